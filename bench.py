@@ -19,9 +19,19 @@ the same step on the pure f32-MFMA kernels is timed in the same process and repo
 Rank 0 prints ONE JSON line with the contract fields plus
   roofline      : the dominant kernel (the CNF solve) -- algorithmic FLOPs per launch / mean launch duration measured with
                   HIP events on the launch stream inside the timed region, vs the peak of the pipe it runs on;
-  cpu_baseline  : the CPU oracle (a port: the reference's own CPU path cannot run) timed on this box's
+  cpu_baseline  : (--full) the CPU oracle (a port: the reference's own CPU path cannot run) timed on this box's
                   host cores on 2 sequences of the same workload, and the ASSERTED parity of the HIP path against it
                   (a failed parity check still prints the line, with "parity_ok": false, and exits non-zero).
+
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line.  Everything else -- the
+per-kernel and stage passes, the f32-MFMA and accuracy-guard sub-blocks, cfg5 / train_cfg3 / stress_dynamics /
+trained_checkpoint, the sharded training step of N > 1, the box calibration and the CPU baseline with its parity checks --
+runs only with --full (the --no-* switches still thin that out); their fields are null otherwise.
+
+--dump-outputs DIR: after the timed steps, the four results of rank 0's last timed reconstruct() call (y, logp_y, x, tnocs;
+None is skipped) as DIR/<name>.npy in float32 (float64 stays float64).  Over 64 MB in all, each array keeps the same fixed,
+seeded subset of its rows (all dimensions but the last flattened).  The inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
 """
 import argparse
 import json
@@ -38,6 +48,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 PEAK_MFMA_F32_TFLOPS = 157.3            # /opt/skills/guides/MI355X_MICROARCH.md: dense f32-input MFMA peak
+DUMP_LIMIT_BYTES = 64 << 20             # --dump-outputs: at most this much in all
 PEAK_MFMA_BF16_TFLOPS = 2500.0          # same guide: dense bf16 MFMA peak; a bf16x6 product costs six of them -> / 6
 CNF_FLOP_PER_POINT_EVAL = 2 * (3 * 512 + 512 * 512 + 512 * 512 + 512 * 3)   # 1,054,720 (no divergence)
 
@@ -86,6 +97,11 @@ def main():
                     help="choose the CNF and latent step counts by step doubling at this tolerance (CaSPR.calibrate_rk4_steps) instead of "
                          "--cnf-steps / --latent-steps; default: 1e-5 with --weights (a trained flow), off (0) on the seeded weights, whose "
                          "headline number is quoted at the fixed, conservative 8 / 2 steps")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: per-kernel / stage passes, the f32-MFMA, accuracy-guard and other-workload "
+                         "sub-blocks, the sharded training step (N > 1), the box calibration, the CPU baseline and the parity checks")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32; a fixed seeded sample of rows beyond 64 MB in all)")
     args = ap.parse_args()
 
     # one process per GPU: a plain `python bench.py --gpus N` starts its own N ranks (torch.distributed.run on 127.0.0.1);
@@ -193,38 +209,42 @@ def main():
     per_rank_ms = [round(1e3 * s_ / args.steps, 3) for s_ in rank_seconds]
     timers = {k: list(v) for k, v in ops.TIMERS.items()}
     mode = ops.matmul_mode()
-    # ---- detail pass (NOT part of the headline timing): one HIP-event pair per launch of the other matrix kernels, for the
-    # per-kernel roofline entries (every rank runs it so that the barriers of the sub-blocks below still pair up)
-    torch.cuda.synchronize()
-    ops.TIMERS.clear()
-    ops.TIMING = 2
-    # (per-kernel durations are measured WITHOUT the accuracy guard's check solve: queued behind a step's flow it runs under the next step's first
-    # millisecond, beside the global PointNet's convs, whose event pairs would otherwise time the contention instead of the kernel -- the 128 -> 1024
-    # layer read 2.2 ms instead of 1.0; the headline above and its own cnf_rk4 launch times are measured with the guard on)
-    # ... and with the global PointNet on the caller's stream: on its own stream (the default schedule) its convs run beside the first
-    # set-abstraction kernels since round 6 (the index chain in front of those got 0.5 ms shorter), and an event pair around a launch then times the
-    # contention: 1.7 ms for the 128 -> 1024 layer against 1.0 ms beside the latency-bound index kernels alone.  The kernel table is about kernels;
-    # the STAGE clocks below come from a second pass on the default schedule with the guard on, as the headline ran.
-    import caspr_amd.models.tpointnet2 as _tp
-    guard_tol, model.check_tol = model.check_tol, None
-    gstream_on, _tp.GLOBAL_STREAM = _tp.GLOBAL_STREAM, False
-    for _ in range(2):
-        step()
-    torch.cuda.synchronize()
-    model.check_tol, _tp.GLOBAL_STREAM = guard_tol, gstream_on
-    ops.TIMING = False
-    detail = {k: [a.elapsed_time(b_) for a, b_ in v] for k, v in ops.TIMERS.items() if k.startswith("k:")}
-    ops.TIMERS.clear()
-    ops.TIMING, ops.TIMING_ONLY = 1, None
-    for _ in range(2):
-        step()
-    torch.cuda.synchronize()
-    ops.TIMING = False
-    stage_timers = {k: list(v) for k, v in ops.TIMERS.items() if not k.startswith("k:")}      # the stage clocks of two steps on the headline's own schedule
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    detail, stage_timers = {}, {}
+    if args.full:
+        # ---- detail pass (NOT part of the headline timing): one HIP-event pair per launch of the other matrix kernels, for the
+        # per-kernel roofline entries (every rank runs it so that the barriers of the sub-blocks below still pair up)
+        torch.cuda.synchronize()
+        ops.TIMERS.clear()
+        ops.TIMING = 2
+        # (per-kernel durations are measured WITHOUT the accuracy guard's check solve: queued behind a step's flow it runs under the next step's first
+        # millisecond, beside the global PointNet's convs, whose event pairs would otherwise time the contention instead of the kernel -- the 128 -> 1024
+        # layer read 2.2 ms instead of 1.0; the headline above and its own cnf_rk4 launch times are measured with the guard on)
+        # ... and with the global PointNet on the caller's stream: on its own stream (the default schedule) its convs run beside the first
+        # set-abstraction kernels since round 6 (the index chain in front of those got 0.5 ms shorter), and an event pair around a launch then times the
+        # contention: 1.7 ms for the 128 -> 1024 layer against 1.0 ms beside the latency-bound index kernels alone.  The kernel table is about kernels;
+        # the STAGE clocks below come from a second pass on the default schedule with the guard on, as the headline ran.
+        import caspr_amd.models.tpointnet2 as _tp
+        guard_tol, model.check_tol = model.check_tol, None
+        gstream_on, _tp.GLOBAL_STREAM = _tp.GLOBAL_STREAM, False
+        for _ in range(2):
+            step()
+        torch.cuda.synchronize()
+        model.check_tol, _tp.GLOBAL_STREAM = guard_tol, gstream_on
+        ops.TIMING = False
+        detail = {k: [a.elapsed_time(b_) for a, b_ in v] for k, v in ops.TIMERS.items() if k.startswith("k:")}
+        ops.TIMERS.clear()
+        ops.TIMING, ops.TIMING_ONLY = 1, None
+        for _ in range(2):
+            step()
+        torch.cuda.synchronize()
+        ops.TIMING = False
+        stage_timers = {k: list(v) for k, v in ops.TIMERS.items() if not k.startswith("k:")}      # the stage clocks of two steps on the headline's own schedule
 
     # ---- the same step on the pure f32-MFMA kernels (sub-block; every rank takes part so the barriers pair up)
     f32_block = None
-    if not args.no_f32_subblock and (ops.CONV_BF16X6 or ops.CNF_BF16X6):
+    if args.full and not args.no_f32_subblock and (ops.CONV_BF16X6 or ops.CNF_BF16X6):
         prev = ops.set_matmul_mode("f32")
         step()
         k32 = max(1, min(args.steps, 3))
@@ -242,7 +262,7 @@ def main():
     # half the steps on a side stream, compared on the device, verdict through the deferred channel as a RuntimeWarning).  The HEADLINE above
     # ran with it; here the same step with the guard OFF, for what it costs -- and what it reported during the headline's timed steps
     guard_block = None
-    if not args.no_guard_subblock and model.check_tol is not None:
+    if args.full and not args.no_guard_subblock and model.check_tol is not None:
         import warnings
         with warnings.catch_warnings(record=True) as wrec:
             warnings.simplefilter("always")
@@ -264,14 +284,14 @@ def main():
     # ---- the other workloads BASELINE.json names, as sub-blocks of the same driver-run line (one GPU only; after the timed region)
     extra = {}
     default_workload = (args.clouds == "cars" and (B, T, N) == (16, 10, 2048) and not args.weights and not args.calibrate_cnf_steps)
-    if world == 1 and not args.no_sub_blocks and default_workload:
+    if args.full and world == 1 and not args.no_sub_blocks and default_workload:
         extra = sub_blocks(args, dev, ops, timed_steps, x, ts)
 
     # ---- N > 1: the one collective north_star names -- cfg-3's training step SHARDED over the ranks (8 sequences of T=10, N=1024 per rank,
     # forward + HIP backward + ONE flat 65 MB gradient all-reduce over RCCL + Adam; bench_train.py's measure(), every rank takes part).
     # The inference value above has no data-path collective (sequences are independent); this is where xGMI carries data.
     train_sharded = None
-    if world > 1 and not args.no_train_subblock:
+    if args.full and world > 1 and not args.no_train_subblock:
         import types
         import bench_train
         tb, tt, tn = (int(v) for v in args.train_shape.split(","))
@@ -339,7 +359,7 @@ def main():
             rc = 1
         if guard_block is not None and guard_block["verdict"] != "quiet" and not args.weights and not args.calibrate_cnf_steps:
             rc = 1            # seeded weights at 8 / 2 steps are converged: a guard that speaks here is a bug
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             cpu, parity_ok = cpu_baseline_and_parity(args, model, sd, ops, dev, out, x, x_all, sp_all, out[0], times_cpu, ts, T, N, dense_sequences)
             if not parity_ok:
                 rc = 1
@@ -362,7 +382,7 @@ def main():
                                  "library": ("gloo (--share-gpu test mode)" if args.share_gpu else collective_library()) if world > 1 else None},
                        "base_samples": "drawn in-step (CPU generator, models/utils.py:25), pinned buffer + async copy under the encoder",
                        "matrix_products": dict(mode, selection=kernel_selection()), "calibration": calibration,
-                       "box": box_calibration() if (world == 1 and not args.no_cpu_baseline) else None,
+                       "box": box_calibration() if (args.full and world == 1 and not args.no_cpu_baseline) else None,
                        "nfe": [int(v) for v in model.get_nfe()]},
             "roofline": roofline, "f32_mfma_path": f32_block, "cfg5": extra.get("cfg5"), "train_cfg3": extra.get("train_cfg3") if world == 1 else train_sharded,
             "stress_dynamics": extra.get("stress_dynamics"), "trained_checkpoint": extra.get("trained_checkpoint"), "accuracy_guard": guard_block, "cpu_baseline": cpu, "parity_ok": parity_ok, "stage_ms_per_step": breakdown,
@@ -383,6 +403,34 @@ def kernel_selection():
     under CASPR_DEBUG=1)."""
     from caspr_amd import config
     return config.active()
+
+
+OUTPUT_NAMES = ("y", "logp_y", "x", "tnocs")       # CaSPR.reconstruct -> (y, logp_y, x, tnocs_pred)
+
+
+def dump_outputs(directory, outputs, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: write reconstruct()'s results as <directory>/<name>.npy, float32 (float64 stays float64), None skipped.
+    Over `limit` bytes in all, every array keeps the same fraction of its rows (all dimensions but the last flattened), chosen by a
+    generator with a fixed seed and kept in their original order.  -> {name: saved shape}."""
+    import numpy as np
+    arrays = {}
+    for name, t in zip(OUTPUT_NAMES, outputs):
+        if t is None:
+            continue
+        a = t.detach().cpu().numpy()
+        arrays[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(directory, exist_ok=True)
+    saved = {}
+    for name, a in arrays.items():
+        if total > limit:
+            rows = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(-1, 1)
+            keep = max(1, int(rows.shape[0] * (limit / total)))
+            idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], keep, replace=False))
+            a = np.ascontiguousarray(rows[idx])
+        np.save(os.path.join(directory, name + ".npy"), a)
+        saved[name] = a.shape
+    return saved
 
 
 def sub_blocks(args, dev, ops, timed_steps, x_headline, ts_headline):

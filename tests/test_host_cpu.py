@@ -680,6 +680,37 @@ def test_bench_box_calibration_is_optional_and_parses_the_micro_benchmark(tmp_pa
     assert bench.box_calibration() is None
 
 
+def test_bench_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    """bench.py --dump-outputs: reconstruct()'s four results as <name>.npy in float32 (float64 kept), None skipped; over the byte limit
+    every array keeps the same seeded subset of its rows, the same from call to call."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    y, x = torch.randn(2, 3, 64, 3, generator=g), torch.randn(2, 3, 64, 3, generator=g)
+    tn = torch.randn(2, 3, 64, 4, generator=g, dtype=torch.float64)
+    saved = bench.dump_outputs(str(tmp_path / "all"), (y, None, x, tn))
+    assert saved == {"y": (2, 3, 64, 3), "x": (2, 3, 64, 3), "tnocs": (2, 3, 64, 4)}
+    assert sorted(os.listdir(tmp_path / "all")) == ["tnocs.npy", "x.npy", "y.npy"]
+    a = np.load(tmp_path / "all" / "x.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, x.numpy())
+    assert np.load(tmp_path / "all" / "tnocs.npy").dtype == np.float64
+    limit = (4 * (y.numel() + x.numel()) + 8 * tn.numel()) // 4          # a quarter of the total
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), (y, None, x, tn), limit=limit)
+    files = sorted(os.listdir(tmp_path / "s1"))
+    assert files == ["tnocs.npy", "x.npy", "y.npy"]
+    assert sum(os.path.getsize(tmp_path / "s1" / f) - 128 for f in files) <= limit       # 128-byte .npy header
+    for f in files:
+        a, b = np.load(tmp_path / "s1" / f), np.load(tmp_path / "s2" / f)
+        assert a.shape[0] == 2 * 3 * 64 // 4 and np.array_equal(a, b)
+    # the sample is a subset of the rows, in order
+    xs, rows = np.load(tmp_path / "s1" / "x.npy"), x.numpy().reshape(-1, 3)
+    idx = [int(np.flatnonzero((rows == r).all(axis=1))[0]) for r in xs]
+    assert idx == sorted(idx) and np.array_equal(rows[idx], xs)
+
+
 def test_step_count_search_refines_between_powers_of_two():
     """CaSPR.calibrate_rk4_steps' search (models/caspr.py:_first_passing) on a synthetic 4th-order error law: the first passing power of
     two is found, then the counts between the last failing one and it are tried where the law predicts they pass -- and every accepted

@@ -72,7 +72,7 @@ def _clean_env():
 def _bench_two_ranks(extra):
     import json
     _free_parent_cache()
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-sub-blocks",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-sub-blocks",
                           "--no-cpu-baseline", "--no-f32-subblock", "--train-shape", "1,2,1024"] + extra, capture_output=True, text=True, timeout=900, env=_clean_env(), cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
