@@ -154,12 +154,26 @@ def test_conv1x1_wgrad_narrow(matmul_mode, B, P, Cin, Cout):
 @pytest.mark.parametrize("B,n,M,ns,C,dims", [(2, 256, 64, 16, 6, (16, 16, 32)), (2, 128, 32, 32, 96, (64, 96, 128)), (1, 64, 16, 32, 512, (256, 256, 512))])
 def test_set_abstraction_scale_backward(B, n, M, ns, C, dims):
     """group -> 3 x (conv -> per-neighbourhood GroupNorm(16) [-> ReLU]) -> max over samples  (pointnet2.py:391-409,649-703):
-    forward output, all parameter gradients and the gradient w.r.t. the input features."""
+    forward output, all parameter gradients and the gradient w.r.t. the input features, through the float-atomic scatter
+    (group_rows_bwd) and through the fixed-order segment gather the training path uses (train_ops.segment_sum)."""
+    _sa_scale_case(B, n, M, ns, C, dims)
+
+
+def test_set_abstraction_scale_backward_centred_first_level():
+    """The first level's 16-channel scale as encoder_grad._sa_scale_fwd builds it: rows centred on the neighbourhood's sample 0, the
+    features prep_input's augmentation of xyz formed from the coordinates (feat_kind = QUAD | PAIRS), no input gradient.  Against the
+    reference's UNcentred grouping: the per-neighbourhood constant cancels in the one-channel GroupNorm groups, forward and backward."""
+    _sa_scale_case(2, 256, 64, 16, 6, (16, 16, 32), centred=True)
+
+
+def _sa_scale_case(B, n, M, ns, C, dims, centred=False):
     from caspr_amd import ops, train_ops as T
+    from oracle import model as O
     dev = "cuda:0"
     g = np.random.default_rng(5)
     xyz = torch.from_numpy(g.uniform(0, 1, (B, n, 3)).astype(np.float32))
-    feat = rnd(11, B, n, C)
+    feat = O.augment_input(xyz)[:, :, 3:].contiguous() if centred else rnd(11, B, n, C)
+    assert feat.shape[2] == C
     idx = torch.from_numpy(g.integers(0, n, (B, M, ns)).astype(np.int32))
     ctr = xyz[:, :M].contiguous()
     R = rnd(12, B, M, dims[2])
@@ -168,8 +182,8 @@ def test_set_abstraction_scale_backward(B, n, M, ns, C, dims):
     bs = [rnd(30 + l, dims[l], scale=0.1) for l in range(3)]
     gs = [1 + rnd(40 + l, dims[l], scale=0.2) for l in range(3)]
     bes = [rnd(50 + l, dims[l], scale=0.2) for l in range(3)]
-    # reference (f64 autograd)
-    f6 = feat.double().requires_grad_(True)
+    # reference (f64 autograd; centred: the augmentation of the same coordinates in f64, what the kernel forms them from)
+    f6 = (O.augment_input(xyz.double())[:, :, 3:] if centred else feat.double()).requires_grad_(True)
     P6 = [[t.double().requires_grad_(True) for t in grp] for grp in (Ws, bs, gs, bes)]
     li = idx.long()
     bi = torch.arange(B).view(B, 1, 1)
@@ -187,7 +201,7 @@ def test_set_abstraction_scale_backward(B, n, M, ns, C, dims):
     featd = F.pad(feat, (0, ldf - C)).to(dev)
     xyzd, ctrd, idxd = xyz.to(dev), ctr.to(dev), idx.to(dev)
     Wd, bd, gd, bed = ([t.to(dev) for t in grp] for grp in (Ws, bs, gs, bes))
-    G = T.group_rows(xyzd, ctrd, featd, C, idxd)
+    G = T.group_rows(xyzd, ctrd, featd, C, idxd, centred=centred, feat_kind=(ops.FEAT_QUAD | ops.FEAT_PAIRS) if centred else 0)
     tape, cur = [], G
     out = torch.empty(B, M, dims[2], device=dev)
     for l in range(3):
@@ -195,7 +209,7 @@ def test_set_abstraction_scale_backward(B, n, M, ns, C, dims):
         A, mean, rstd, arg = T.gn_rows(y, ns, dims[l], gd[l], bed[l], relu=l < 2, maxout=out if l == 2 else None)
         tape.append((cur, y, mean, rstd, arg))
         cur = A
-    tag = "[%d,%d,%s]" % (C, ns, "-".join(map(str, dims)))
+    tag = "[%d,%d,%s%s]" % (C, ns, "-".join(map(str, dims)), ",centred" if centred else "")
     rel("sa_fwd" + tag, out, out6, 2e-5)
     dout = R.to(dev).contiguous()
     d = None
@@ -213,9 +227,18 @@ def test_set_abstraction_scale_backward(B, n, M, ns, C, dims):
         rel("sa_db%d" % l + tag, db, P6[1][l].grad, 1e-4, ref=float(P6[0][l].grad.abs().max()))
         rel("sa_dgamma%d" % l + tag, dg, P6[2][l].grad, 1e-4)
         rel("sa_dbeta%d" % l + tag, dbe, P6[3][l].grad, 1e-4)
+    if centred:
+        return                  # (no input gradient on this route: the first level's input is the data)
     dfeat = torch.zeros(B, n, ldf, device=dev)
     T.group_rows_bwd(d, idxd, C, dfeat)
     rel("sa_dfeat" + tag, dfeat[:, :, :C], f6.grad, 1e-4)
+    # the production form: fixed-order gather over the segments encoder_grad._sa_scale_fwd builds, into a non-zero dfeat
+    base = (torch.arange(B, device=dev, dtype=torch.int64) * n).view(B, 1, 1)
+    seg = T.Segments(idxd.long() + base, B * n)
+    init = rnd(13, B, n, ldf).to(dev)
+    dfeat_s = init.clone()
+    T.segment_sum(d, seg, C, dfeat_s, col0=3, accumulate=True)
+    rel("sa_dfeat_segment" + tag, dfeat_s[:, :, :C] - init[:, :, :C], f6.grad, 1e-4)
 
 
 def test_three_interp_backward():
@@ -233,6 +256,13 @@ def test_three_interp_backward():
     dfeat = torch.zeros(B, m, C, device=dev)
     T.three_interp_bwd(R.to(dev), idx, w, C, dfeat)
     rel("three_interp_bwd", dfeat, f6.grad, 1e-5)
+    # the production form (encoder_grad.py, feature-propagation backward): the fixed-order gather over three-NN segments
+    base = (torch.arange(B, device=dev, dtype=torch.int64) * m).view(B, 1, 1)
+    rows = torch.arange(B * n, device=dev, dtype=torch.int64).view(B, n, 1).expand(B, n, 3)
+    seg = T.Segments(idx.long() + base, B * m, weight=w, src_rows=rows)
+    dfeat_s = torch.zeros(B, m, C, device=dev)
+    T.segment_sum(R.to(dev), seg, C, dfeat_s, col0=0, accumulate=True)
+    rel("three_interp_bwd_segment", dfeat_s, f6.grad, 1e-5)
 
 
 def test_head_max_backward():
