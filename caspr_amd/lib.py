@@ -88,6 +88,9 @@ SIGNATURES = {
     "caspr_chamfer_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_stream]),
     "caspr_emd_ws_bytes": (c_long, [c_int, c_int, c_int]),
     "caspr_emd_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp, ctypes.c_void_p, c_long, c_stream]),
+    "caspr_pose_ransac_ws_bytes": (c_long, [c_int, c_int, c_int]),
+    "caspr_pose_ransac_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_ulonglong, c_int,
+                                      ctypes.c_void_p, c_ip, ctypes.c_void_p, c_ip, ctypes.c_void_p, c_long, c_stream]),
     # ---- include/caspr_hip_train.h (training tier) ----
     "caspr_gn_stats_train_f32": (c_int, [c_fp, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp, c_float, c_fp, c_fp, c_fp, c_fp, c_fp,
                                          ctypes.c_void_p, c_long, c_stream]),

@@ -949,3 +949,45 @@ def earth_mover_distance(xyz1, xyz2, transpose=True):
     ws = _workspace(L.caspr_emd_ws_bytes(B, n, m), xyz1.device)
     _lib.check(L.caspr_emd_f32(_p(xyz1), _p(xyz2), B, n, m, _p(cost), _p(ws), ws.numel(), _stream()), "caspr_emd_f32")
     return cost
+
+
+def ransac_rigid_from_correspondences(src, dst, threshold=0.015, num_hypotheses=5000, sample_size=4, seed=0, refine=False):
+    """Open3D `registration_ransac_based_on_correspondence` with point-to-point estimation without scaling, as the camera-pose
+    evaluation calls it (evaluations.py:370-375: ransac_n = 4, threshold 0.015, RANSACConvergenceCriteria(50000, 5000) ->
+    5000 hypotheses), for correspondences src_i <-> dst_i given index for index (csrc/pose.hip; parity UNPINNED).
+
+    src, dst: (F,N,3|4) or (N,3|4) float GPU tensors of the same shape (only x, y, z are read).  The hypotheses come from a counter
+    hash of `seed`: one seed gives bitwise-equal results.  refine: refit on the winner's inliers and report the refit's score.
+    -> T (F,4,4) f64 with dst ~ T[:3,:3] src + T[:3,3], fitness (F,) f64, inlier_rmse (F,) f64, inliers (F,) int32, best (F,) int32."""
+    if src.dim() == 2:
+        src = src.unsqueeze(0)
+    if dst.dim() == 2:
+        dst = dst.unsqueeze(0)
+    if src.dim() != 3 or src.shape[2] not in (3, 4):
+        raise ValueError("src must be (F,N,3|4) or (N,3|4), got %s" % (tuple(src.shape),))
+    if dst.shape[:2] != src.shape[:2] or dst.shape[2] not in (3, 4):
+        raise ValueError("dst %s does not match src %s" % (tuple(dst.shape), tuple(src.shape)))
+    if src.shape[2] != dst.shape[2]:   # one row stride for both clouds
+        src, dst = src[..., :3], dst[..., :3]
+    F, N, rs = src.shape
+    n, K = int(sample_size), int(num_hypotheses)
+    if not 3 <= n <= 8:
+        raise ValueError("sample_size must lie in 3..8, got %d" % n)
+    if N < n:
+        raise ValueError("%d correspondences, fewer than the sample size %d" % (N, n))
+    if K < 1:
+        raise ValueError("num_hypotheses must be positive, got %d" % K)
+    if not (threshold > 0 and threshold < float("inf")):
+        raise ValueError("threshold must be positive and finite, got %r" % (threshold,))
+    src, dst = src.contiguous().float(), dst.contiguous().float()
+    _chk_f32(src, dst)
+    dev = src.device
+    T = torch.empty(F, 4, 4, device=dev, dtype=torch.float64)
+    rmse = torch.empty(F, device=dev, dtype=torch.float64)
+    inliers = torch.empty(F, device=dev, dtype=torch.int32)
+    best = torch.empty(F, device=dev, dtype=torch.int32)
+    L = _lib.load()
+    ws = _workspace(L.caspr_pose_ransac_ws_bytes(F, N, K), dev)
+    _lib.check(L.caspr_pose_ransac_f32(_p(src), _p(dst), F, N, rs, K, n, float(threshold), int(seed) & 0xFFFFFFFFFFFFFFFF, int(bool(refine)),
+                                       _p(T), _p(inliers), _p(rmse), _p(best), _p(ws), ws.numel(), _stream()), "caspr_pose_ransac_f32")
+    return T, inliers.double() / N, rmse, inliers, best

@@ -3,7 +3,10 @@
 Metric side of BASELINE.json's headline ("sequences/sec + Chamfer-L2"): the paper's protocol evaluates 10 steps x 2048
 points, either all steps observed or steps [0,5,9] observed / [1,2,3,4,6,7,8] unobserved (evaluations.py:26-34), with
 Chamfer = mean_i min_j |p_i-g_j|^2 + mean_j min_i |.|^2 per frame (evaluations.py:36-44; printed x1000) and the
-approximate EMD / N (evaluations.py:45-46, caspr_emd_f32).  The RANSAC pose eval is out of scope.
+approximate EMD / N (evaluations.py:45-46, caspr_emd_f32).  The camera-pose evaluation (evaluations.py:297-513) fits the
+rigid transform from predicted T-NOCS to the observed points with the correspondence RANSAC of csrc/pose.hip
+(ops.ransac_rigid_from_correspondences) in place of Open3D's; its parity with the Open3D release the reference calls is
+UNPINNED (DESIGN.md section 5): the hypotheses come from a seeded counter hash, not from the clock-seeded std::rand.
 Differences from the reference, on purpose: bad protocol sizes raise ValueError instead of exit(); the inference
 timer synchronises the device (evaluations.py:108-115 does not)."""
 import time
@@ -93,6 +96,53 @@ def test_tnocs_regression(model, batches, device, protocol=True):
     return {"space": _stats(space), "time": _stats(tdiff)}
 
 
+def test_observed_camera_pose_ransac(model, batches, device, protocol=True, threshold=0.015, num_hypotheses=5000, seed=0, refine=False):
+    """evaluations.py:297-513.  `batches` yields (pcl_in (B,T,N,4), nocs_out (B,T,N,4), pose (B,T,4,4)), the pose as
+    DynamicPCLDataset.set_return_pose_data(True) provides it.  Per observed frame the rigid transform from the predicted T-NOCS
+    (minus 0.5) to the input points, index for index, by RANSAC (evaluations.py:370-375: ransac_n = 4, threshold 0.015, 5000
+    hypotheses; one op call for all B*T frames of a batch), then in f64 on the device (evaluations.py:380-430):
+      trans = |t_pred - t_gt|,  rot = degrees(arccos(clip((tr(R_pred^T R_gt) - 1) / 2, -1, 1))),
+      point / point_mean = median / mean over points of |R_pred (gt_nocs - 0.5) + t_pred - input|.
+    Returns _stats of each ("trans", "rot", "point", "point_mean"), the per-frame lists ("per_frame") and the per-sequence means
+    the reference writes to its CSV ("per_sequence"); nothing is written to disk."""
+    model.eval()
+    per = {"trans": [], "rot": [], "point": [], "point_mean": []}
+    steps = None
+    for pcl_in, nocs_out, pose in batches:
+        pcl_in, nocs_out = pcl_in.to(device), nocs_out.to(device)
+        B, T, N, _ = pcl_in.size()
+        if protocol and T != PROTOCOL_NUM_STEPS:
+            raise ValueError('Test protocol requires %d steps, but %d given!' % (PROTOCOL_NUM_STEPS, T))
+        if protocol and N != PROTOCOL_NUM_PTS:
+            raise ValueError('Test protocol requires %d points, but %d given!' % (PROTOCOL_NUM_PTS, N))
+        if steps is not None and T != steps:
+            raise ValueError('every batch needs the same number of steps (%d, then %d)' % (steps, T))
+        steps = T
+        with torch.no_grad():
+            _, pred_tnocs = model.encode(pcl_in)
+        # src = predicted T-NOCS - 0.5, dst = the input points; both (B*T,N,4) rows, of which the kernel reads x, y, z
+        Tp, _, _, _, _ = ops.ransac_rigid_from_correspondences((pred_tnocs - 0.5).reshape(B * T, N, -1), pcl_in.reshape(B * T, N, -1),
+                                                               threshold=threshold, num_hypotheses=num_hypotheses, seed=seed, refine=refine)
+        R_pred, t_pred = Tp[:, :3, :3], Tp[:, :3, 3]
+        pose = pose.to(device=device, dtype=torch.float64).reshape(B * T, 4, 4)
+        R_gt, t_gt = pose[:, :3, :3], pose[:, :3, 3]
+        trans = torch.linalg.norm(t_pred - t_gt, dim=1)
+        cos = torch.clamp(((R_pred * R_gt).sum(dim=(1, 2)) - 1.0) / 2.0, -1.0, 1.0)    # tr(R_pred^T R_gt) = sum_ij R_pred,ij R_gt,ij
+        rot = torch.rad2deg(torch.arccos(cos))
+        gt_nocs = (nocs_out[:, :, :, :3] - 0.5).reshape(B * T, N, 3).double()          # f32 subtraction, as the reference's tensors
+        inp = pcl_in[:, :, :, :3].reshape(B * T, N, 3).double()
+        dist = torch.linalg.norm(torch.matmul(gt_nocs, R_pred.transpose(1, 2)) + t_pred[:, None, :] - inp, dim=2)
+        srt = torch.sort(dist, dim=1).values                                             # np.median: the mean of the middle two
+        median = srt[:, N // 2] if N % 2 else (srt[:, N // 2 - 1] + srt[:, N // 2]) / 2.0
+        for k, v in (("trans", trans), ("rot", rot), ("point", median), ("point_mean", dist.mean(dim=1))):
+            per[k].extend(v.cpu().numpy().tolist())
+    out = {k: _stats(v) for k, v in per.items()}
+    out["per_frame"] = per
+    out["per_sequence"] = {k: (np.asarray(v).reshape(-1, steps).mean(axis=1).tolist() if v else []) for k, v in per.items()}
+    return out
+
+
 # keep pytest from collecting the reference-named entry points of this module
 test_shape_recon.__test__ = False
 test_tnocs_regression.__test__ = False
+test_observed_camera_pose_ransac.__test__ = False

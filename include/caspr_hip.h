@@ -345,6 +345,19 @@ long caspr_emd_ws_bytes(int B, int n, int m);
 int caspr_emd_f32(const float *xyz1, const float *xyz2, int B, int n, int m, float *cost, void *ws,
                   long ws_bytes, void *stream);
 
+/* ---------------- correspondence RANSAC for a rigid pose (utils/evaluations.py:297-437, the camera-pose evaluation;
+ * call site evaluations.py:370-375: Open3D registration_ransac_based_on_correspondence, ransac_n = 4, threshold 0.015,
+ * RANSACConvergenceCriteria(50000, 5000), point-to-point without scaling) -- src, dst (F,N,row_stride) f32 with
+ * row_stride 3 or 4 (x, y, z read; correspondence i is src_i <-> dst_i), K hypotheses of n indices (3 <= n <= 8) drawn by a
+ * counter hash of (seed, frame, hypothesis, draw), Horn's f64 estimate, inliers |R src_i + t - dst_i| < threshold; per frame
+ * T (F,4,4) f64 [R t; 0 0 0 1] with dst ~ R src + t, inliers (F), inlier rmse (F) f64, best hypothesis (F).  refine = 1 refits
+ * on the winner's inliers and scores the refit.  Hash, estimator and selection order: csrc/pose.hip.  Parity with the Open3D
+ * release the reference calls is UNPINNED.  ws >= caspr_pose_ransac_ws_bytes(F,N,K).              */
+long caspr_pose_ransac_ws_bytes(int F, int N, int K);
+int caspr_pose_ransac_f32(const float *src, const float *dst, int F, int N, int row_stride, int K, int n,
+                          double threshold, unsigned long long seed, int refine, double *T, int *inliers,
+                          double *rmse, int *best, void *ws, long ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
