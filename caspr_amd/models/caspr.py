@@ -135,7 +135,7 @@ class CaSPR(nn.Module):
     def __init__(self, radii_list=[0.02, 0.05, 0.1, 0.2, 0.4, 0.8], local_feat_size=512, latent_feat_size=1600,
                  ode_hidden_size=512, motion_feat_size=64, pretrain_tnocs=False, augment_quad=True, augment_pairs=True,
                  cnf_blocks=1, regress_tnocs=True, *, cnf_rk4_steps=8, latent_rk4_steps=2, check_tol=1e-5, latent_check_tol=None,
-                 check_action="warn", check_points=64):
+                 check_action="warn", check_points=64, cnf_method="rk4", cnf_atol=1e-5, cnf_rtol=1e-5):
         super(CaSPR, self).__init__()
         # Run-time accuracy guard of the fixed-step integrators: ON by default at the reference's own tolerances, reporting as a
         # RuntimeWarning (check_action="raise": CasprAccuracyError; check_tol=None: off).  The reference's dopri5 controls its error at every
@@ -168,6 +168,11 @@ class CaSPR(nn.Module):
         self.cnf_args.zdim = latent_feat_size
         self.cnf_args.num_blocks = cnf_blocks
         self.cnf_args.rk4_steps = cnf_rk4_steps
+        # cnf_method="dopri5": the point CNF integrates to cnf_atol / cnf_rtol with the adaptive kernel (inference only; per-frame error
+        # control); the accuracy guard and calibrate_rk4_steps then have nothing to halve and skip the block
+        self.cnf_args.method = cnf_method
+        self.cnf_args.atol = cnf_atol
+        self.cnf_args.rtol = cnf_rtol
         self.point_cnf = get_point_cnf(self.cnf_args)
 
     # ------------------------------------------------------------------------------------------
@@ -303,7 +308,9 @@ class CaSPR(nn.Module):
         logpx / e given: the density direction of forward() (cnf.py:70-128 with the Hutchinson divergence, same noise on the same
         samples); otherwise the sampling direction of decode()."""
         from .cnf import CNF
-        blocks = [l for l in self.point_cnf.chain if isinstance(l, CNF)]
+        blocks = [l for l in self.point_cnf.chain if isinstance(l, CNF) and l.method == "rk4"]
+        if not blocks or len(blocks) != sum(isinstance(l, CNF) for l in self.point_cnf.chain):
+            return None           # dopri5 blocks control their own error: no step count to halve, no check solve
         for b in blocks:
             b._weights()
             if ops.CNF_BF16X6:
@@ -514,7 +521,7 @@ class CaSPR(nn.Module):
         The reference's dopri5 runs at atol = rtol = 1e-5 (flow.py:96-99; 1e-3 for the latent ODE, latent_ode_model.py:38,83);
         the defaults of this build (8 steps, 2 per interval) are kept unless this is called."""
         from .cnf import CNF
-        blocks = [l for l in self.point_cnf.chain if isinstance(l, CNF)]
+        blocks = [l for l in self.point_cnf.chain if isinstance(l, CNF) and l.method == "rk4"]       # a dopri5 block has no step count
         guard, self.check_tol = self.check_tol, None          # the candidates below are MEANT to be under-resolved: no guard while choosing
         try:
             return self._calibrate(blocks, x, tol, candidates, num_points, timestamps, max_timestamp, latent_tol, latent_candidates, refine, rtol)

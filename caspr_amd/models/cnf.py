@@ -5,6 +5,10 @@ through torchdiffeq (cnf.py:100-119, flow.py:96-99); this build runs `rk4_steps`
 over [0, sqrt_end_time^2] inside ONE kernel launch.  When no log-density is requested (sampling,
 cnf.py:71-74 with logpx=None) the Hutchinson divergence is skipped: with a fixed step the xyz
 trajectory does not depend on it.
+
+OPTION `method="dopri5"` (inference only): the reference's adaptive solve at `test_atol / test_rtol` on the
+GPU (ops.cnf_dopri5, csrc/ode_dp5.hip), error control per frame; `get_nfe()` then reports the measured
+maximum over frames.  RK4 stays the default and the training path.
 """
 import torch
 import torch.nn as nn
@@ -18,7 +22,7 @@ __all__ = ["CNF", "SequentialFlow"]
 
 class CNF(nn.Module):
     def __init__(self, odefunc, conditional=True, T=1.0, train_T=False, solver='dopri5', atol=1e-5, rtol=1e-5,
-                 use_adjoint=True, rk4_steps=8):
+                 use_adjoint=True, rk4_steps=8, method="rk4", max_attempts=1000):
         super(CNF, self).__init__()
         self.train_T = train_T
         self.T = T
@@ -35,6 +39,11 @@ class CNF(nn.Module):
         self.solver_options = {}
         self.conditional = conditional
         self.rk4_steps = rk4_steps
+        if method not in ("rk4", "dopri5"):
+            raise ValueError("CNF method must be 'rk4' or 'dopri5', got %r" % (method,))
+        self.method = method          # "dopri5": integrate() solves to test_atol / test_rtol (inference only)
+        self.max_attempts = max_attempts
+        self.last_nfe_per_frame = None   # dopri5: (BT,) int32 device tensor of the last counted solve
         self._count_evals = True      # False while the accuracy guard repeats a solve (CaSPR._guard_cnf): get_nfe() counts the real one only
         self._narrow = False          # True while the guard runs its check solve: the 64-point sampling kernel (ops.cnf_rk4(narrow=True))
         self._cache = WeightCache()
@@ -100,6 +109,21 @@ class CNF(nn.Module):
         if ops.BEFORE_CNF_LAUNCH is not None and self._count_evals:      # (not for the accuracy guard's check solve)
             hook, ops.BEFORE_CNF_LAUNCH = ops.BEFORE_CNF_LAUNCH, None
             hook()
+        if self.method == "dopri5":
+            if torch.is_grad_enabled():
+                raise ValueError("CNF(method='dopri5') is an inference option: no gradient through the adaptive solve (training keeps RK4)")
+            if torch.cuda.is_current_stream_capturing():
+                raise ValueError("CNF(method='dopri5') cannot run under stream capture: the host loop reads the device after every attempt")
+            if w1x is None:
+                raise ValueError("CNF(method='dopri5') needs the bf16x6 kernel (ops.CNF_BF16X6, 512-512-512)")
+            res = ops.cnf_dopri5(x.contiguous(), hyper, w["tcol"], w["w0"], w["b0"], w["b1"], w["b2"], w["w3"], w["b3"], w1x, w2x,
+                                 self.end_time(), self.test_rtol, self.test_atol, reverse, mbn_in, mbn_out, e=e,
+                                 logp=None if logpx is None else logpx.contiguous(), max_attempts=self.max_attempts, return_trace=True)
+            info, res = res[-1], (res[0] if logpx is None else res[:-1])
+            if self._count_evals:
+                self.last_nfe_per_frame = info["nfe"]
+                self.odefunc._num_evals += info["nfe"].max().to(self.odefunc._num_evals.dtype)
+            return res
         res = ops.cnf_rk4(x.contiguous(), hyper, w["tcol"], w["w0"], w["b0"], w["w1p"], w["b1"], w["w2p"], w["b2"], w["w3"], w["b3"],
                           self.end_time(), self.rk4_steps, reverse, mbn_in, mbn_out, e=e,
                           logp=None if logpx is None else logpx.contiguous(), w1x=w1x, w2x=w2x, narrow=self._narrow)

@@ -25,10 +25,11 @@ def count_parameters(model):
 
 class PointCNFArgs:
     """Options of the point CNF with the reference's defaults (flow.py:86-100).  `rk4_steps` is this build's own knob: the
-    number of fixed RK4 steps that replaces dopri5 at atol = rtol = 1e-5."""
+    number of fixed RK4 steps that replaces dopri5 at atol = rtol = 1e-5.  `method`: "rk4" (default) or
+    "dopri5" -- the adaptive solve at atol / rtol on the GPU, inference only (`solver` is the reference's field and stays unread)."""
     DEFAULTS = dict(input_dim=3, dims="512-512-512", zdim=512, num_blocks=1, layer_type="concatsquash", nonlinearity="softplus",
                     time_length=0.5, train_T=True, solver="dopri5", use_adjoint=True, atol=1e-5, rtol=1e-5, batch_norm=True,
-                    rk4_steps=8)
+                    rk4_steps=8, method="rk4")
 
     def __init__(self, **overrides):
         unknown = set(overrides) - set(self.DEFAULTS)
@@ -42,7 +43,7 @@ def _cnf_block(args, input_dim, hidden_dims, context_dim, conditional):
     net = ODEnet(hidden_dims=hidden_dims, input_shape=(input_dim,), context_dim=context_dim, layer_type=args.layer_type,
                  nonlinearity=args.nonlinearity)
     return CNF(odefunc=ODEfunc(diffeq=net), T=args.time_length, train_T=args.train_T, conditional=conditional, solver=args.solver,
-               atol=args.atol, rtol=args.rtol, use_adjoint=args.use_adjoint, rk4_steps=args.rk4_steps)
+               atol=args.atol, rtol=args.rtol, use_adjoint=args.use_adjoint, rk4_steps=args.rk4_steps, method=args.method)
 
 
 def build_model(args, input_dim, hidden_dims, context_dim, num_blocks, conditional):

@@ -100,7 +100,8 @@ class ODESolver(nn.Module):
             raise ValueError('ode_func is required to be an instance of nn.Module to use the adjoint method')
 
     def forward(self, z0, t):
-        raise NotImplementedError("the adaptive solver is replaced by LatentODE's RK4 kernel; call LatentODE.forward")
+        raise NotImplementedError("the adaptive solver is replaced by LatentODE's RK4 kernel; call LatentODE.forward "
+                                  "(the GPU dopri5 option, CaSPR(cnf_method='dopri5'), covers the point CNF only: the latent ODE stays RK4)")
 
 
 class DynamicsNet(nn.Module):

@@ -920,6 +920,62 @@ def cnf_rk4(y, hyper, tcol, w0, b0, w1p, b1, w2p, b2, w3, b3, t_end, steps, reve
     return out if e is None else (out, lp_out)
 
 
+DP5_TRACE_HEAD, DP5_TRACE_ROW = 8, 5      # include/caspr_hip.h: the trace layout of caspr_cnf_dopri5_f32
+
+
+def cnf_dopri5(y, hyper, tcol, w0, b0, b1, b2, w3, b3, w1x, w2x, t_end, rtol, atol, reverse, mbn_in=None, mbn_out=None,
+               e=None, logp=None, max_attempts=1000, return_trace=False):
+    """Adaptive Dormand-Prince 5(4) solve of one CNF block to a tolerance (cnf.py:96-118: what the reference runs on every call), error
+    control PER FRAME (csrc/ode_dp5.hip).  Arguments as cnf_rk4 with the bf16x6 packs w1x / w2x (pack_cnf_x6) required.  Returns x or
+    (x, logp); with return_trace a dict is appended: "d0", "d1", "d2", "h0", "dt0" (BT,), "attempts" (BT, max_attempts, 5) rows
+    [t, dt, ratio x, ratio logp, accepted], "accepted", "rejected", "nfe" (BT,) int32 -- all on the device.
+    The host reads one device word per attempt: not usable under stream capture or with autograd (training keeps RK4).
+    Raises CasprHipError when a frame has not reached t_end after max_attempts attempts."""
+    _chk_f32(y, hyper, tcol, w0, b0, b1, b2, w3, b3, mbn_in, mbn_out, e, logp)
+    if y.dim() != 3 or y.shape[2] != 3:
+        raise ValueError("cnf_dopri5: y must be (BT,n,3), got %s" % (tuple(y.shape),))
+    BT, n, _ = y.shape
+    if hyper.dim() != 2 or hyper.shape[0] != BT:
+        raise ValueError("cnf_dopri5: hyper has %s rows for %d frames" % (tuple(hyper.shape), BT))
+    if (e is None) != (logp is None):
+        raise ValueError("cnf_dopri5: the Hutchinson noise e and the initial log-density come together")
+    if e is not None and (tuple(e.shape) != tuple(y.shape) or tuple(logp.shape) != (BT, n, 1)):
+        raise ValueError("cnf_dopri5: e %s / logp %s do not match y %s" % (tuple(e.shape), tuple(logp.shape), tuple(y.shape)))
+    for name, m_ in (("mbn_in", mbn_in), ("mbn_out", mbn_out)):
+        if m_ is not None and m_.numel() != 12:
+            raise ValueError("cnf_dopri5: %s must hold 12 floats [weight | bias | running_mean | running_var]" % name)
+    if w1x is None or w2x is None:
+        raise ValueError("cnf_dopri5: the bf16x6 weight packs w1x / w2x (pack_cnf_x6) are required")
+    rtol, atol, max_attempts = float(rtol), float(atol), int(max_attempts)
+    if not (0 < rtol < float("inf") and 0 < atol < float("inf")):
+        raise ValueError("cnf_dopri5: rtol and atol must be positive and finite, got %r / %r" % (rtol, atol))
+    if not (0 < float(t_end) < float("inf")):
+        raise ValueError("cnf_dopri5: t_end must be positive and finite, got %r" % (t_end,))
+    if max_attempts < 1:
+        raise ValueError("cnf_dopri5: max_attempts must be positive, got %d" % max_attempts)
+    if torch.is_grad_enabled() and any(t_ is not None and t_.requires_grad for t_ in (y, hyper, e, logp)):
+        raise ValueError("cnf_dopri5: no gradient through the adaptive solve (training keeps RK4)")
+    if torch.cuda.is_current_stream_capturing():
+        raise ValueError("cnf_dopri5: the host loop reads the device after every attempt and cannot run under stream capture")
+    out = torch.empty_like(y)
+    lp_out = torch.empty(BT, n, 1, device=y.device, dtype=torch.float32) if e is not None else None
+    trace = torch.empty(BT, DP5_TRACE_HEAD + DP5_TRACE_ROW * max_attempts, device=y.device, dtype=torch.float32)
+    counters = torch.empty(BT, 4, device=y.device, dtype=torch.int32)
+    L = _lib.load()
+    ws = _workspace(L.caspr_cnf_dopri5_ws_bytes(BT, n, max_attempts), y.device)
+    with timed("cnf_dopri5"):
+        _lib.check(L.caspr_cnf_dopri5_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1x), _p(b1), _p(w2x), _p(b2), _p(w3), _p(b3),
+                                          w0.shape[0], float(t_end), rtol, atol, max_attempts, int(bool(reverse)), _p(mbn_in), _p(mbn_out),
+                                          _p(e), _p(logp), _p(lp_out), _p(out), BT, n, _p(ws), ws.numel(), _p(trace), _p(counters), _stream()),
+                   "caspr_cnf_dopri5_f32")
+    res = (out,) if e is None else (out, lp_out)
+    if return_trace:
+        res = res + ({"d0": trace[:, 0], "d1": trace[:, 1], "d2": trace[:, 2], "h0": trace[:, 3], "dt0": trace[:, 4],
+                      "attempts": trace[:, DP5_TRACE_HEAD:].view(BT, max_attempts, DP5_TRACE_ROW),
+                      "accepted": counters[:, 0], "rejected": counters[:, 1], "nfe": counters[:, 2]},)
+    return res[0] if len(res) == 1 else res
+
+
 def chamfer_distance(p, q):
     """tk3dv `ChamferDistance()(pred, gt)` (evaluations.py:40): -> dist1 (B,n), dist2 (B,m) squared NN distances."""
     _chk_f32(p, q)

@@ -32,6 +32,7 @@ extern "C" {
 #define CASPR_EINVAL (-1)   /* bad argument (shape / alignment / null pointer)         */
 #define CASPR_ELAUNCH (-2)  /* hipLaunchKernel / hipGetLastError reported a failure    */
 #define CASPR_EUNSUP (-3)   /* shape outside what the kernels are instantiated for     */
+#define CASPR_ENOCONV (-4)  /* an adaptive solve used up its attempt budget (caspr_cnf_dopri5_f32) */
 
 const char *caspr_last_error_string(void);
 int caspr_abi_version(void);
@@ -331,6 +332,28 @@ int caspr_cnf_rk4_x6_f32(const float *y_in, const float *hyper, int ldh, const f
                          float t_end, int steps, int reverse, const float *mbn_in, const float *mbn_out,
                          const float *e, const float *logp_in, float *logp_out, float *y_out, int BT,
                          int n, void *stream);
+
+/* ---------------- adaptive Dormand-Prince 5(4) solve of the same CNF block: models/cnf.py:96-118 (odeint with
+ * method = dopri5, atol / rtol) -- what the reference runs on every call.  torchdiffeq 0.0.1's algorithm as oracle.model.dopri5_solve
+ * restates it (initial step from d0 / d1 / d2, tol = atol + rtol max(|y0|, |y1|) per tensor of the state (x, logp), ratio =
+ * mean((err / tol)^2), accept iff both ratios <= 1, safety 0.9 / 10 / 0.2, FSAL, integration past t_end and the 4th-order interpolant
+ * there), with ONE difference: the norms are taken PER FRAME (row of BT), so a frame's result is what the reference computes when it
+ * is called on that frame alone, bit for bit whatever batch surrounds it.  csrc/ode_dp5.hip: the evaluation of the 64-point bf16x6
+ * kernel, one launch per attempt.  Arguments as caspr_cnf_rk4_x6_f32 with `steps` replaced by rtol, atol, max_attempts, plus
+ *   ws        >= caspr_cnf_dopri5_ws_bytes(BT, n, max_attempts) bytes, 256-byte aligned (carry-over between launches);
+ *   trace     (BT, 8 + 5 max_attempts) f32: [d0, d1, d2, h0, first dt, 0, 0, 0] then per attempt [t, dt, ratio x, ratio logp, accepted];
+ *   counters  (BT, 4) int32: accepted, rejected, function evaluations, finished.
+ * UNLIKE every other entry point this one SYNCHRONISES the stream: after each attempt the host reads one device word (frames still
+ * running) and stops launching when it is zero.  CASPR_ENOCONV when a frame has not reached t_end after max_attempts attempts (its
+ * output rows are then undefined), CASPR_EUNSUP under stream capture.                                                       */
+long caspr_cnf_dopri5_ws_bytes(int BT, int n, int max_attempts);
+int caspr_cnf_dopri5_f32(const float *y_in, const float *hyper, int ldh, const float *tcol,
+                         const float *w0, const float *b0, const void *w1x, const float *b1,
+                         const void *w2x, const float *b2, const float *w3, const float *b3, int H,
+                         float t_end, float rtol, float atol, int max_attempts, int reverse,
+                         const float *mbn_in, const float *mbn_out, const float *e, const float *logp_in,
+                         float *logp_out, float *y_out, int BT, int n, void *ws, long ws_bytes,
+                         float *trace, int32_t *counters, void *stream);
 
 /* ---------------- Chamfer (tk3dv.extern.chamfer.ChamferDistance): utils/evaluations.py:40 --------
  * p (B,n,3), q (B,m,3) -> dist1 (B,n) = min_j |p_i-q_j|^2 , dist2 (B,m).                            */
