@@ -1,0 +1,373 @@
+// ode_latent_dp5.hip -- the latent ODE (latent_ode_model.py:45-70) integrated to a TOLERANCE: adaptive Dormand-Prince 5(4) as
+// torchdiffeq 0.0.1 runs it (oracle.model.dopri5_solve restates it), the whole solve in ONE launch with the step control on the
+// device.  ONE difference from the reference, the one the point-CNF solve of ode_dp5.hip makes: norms and decisions are taken PER
+// SEQUENCE (row of B), not over the whole (B, D) tensor -- a sequence's codes are what the reference computes when it is called
+// on that sequence alone, whatever batch surrounds it.
+//
+// The evaluation is the one of latent_rk4_kernel (ode.hip), copied: one 512-thread workgroup advects up to 16 sequences as the 16
+// columns of the f32 MFMA tile, each wave owns 64 of the 512 hidden units and streams its packed weights from L2 once per
+// evaluation for all columns, the hidden state is an LDS B-tile.  What differs is the loop around it:
+//  * the dynamics do not read t, so every column carries ITS OWN t, dt, next-stamp cursor and finished flag.  Attempts run in
+//    lockstep (six evaluations each, the seventh stage is the next attempt's first: FSAL), every column with its own dt; a column
+//    that has emitted its last stamp, and a padding column, runs with dt = 0 and is neither read nor written by the control phase.
+//    MFMA columns are independent, so a column never sees its neighbours;
+//  * the control phase is wave-local: wave w owns columns 2w and 2w + 1, lane d holds component d.  The sum of squares of a norm
+//    is an f64 xor-butterfly over the 64 lanes -- one fixed order, every lane ends with the same bits -- so all lanes take the
+//    identical accept / reject decision and the identical next dt (f32, as ode_dp5.hip), without atomics or a designated thread;
+//  * steps are not clipped at the output stamps: after an accepted step the wave emits every stamp up to the step's end from the
+//    4th-order interpolant (y_new itself at the step's end, z0 at stamps equal to times[0]); repeated stamps evaluate the same
+//    polynomial at the same abscissa and give the same bits;
+//  * the loop ends when all 16 columns have finished or max_attempts rounds have run.  The exit test reads the 16 finished flags
+//    from LDS behind a barrier: workgroup-uniform, every thread passes the same barriers.  A sequence that has not finished gets
+//    finished = 0 and NaN in the rows it did not reach.
+// No inter-workgroup communication, no co-residency requirement, no host read: the launch can be captured.
+// A sequence's output, trace and counters are bit-identical whichever column, workgroup or batch it sits in.
+#include <math.h>
+#include <stdlib.h>
+
+#include "common.h"
+
+#define LDP_NCOL 16
+#define LDP_EL (64 * LDP_NCOL)    // one state array: [d][c]
+#define LDP_TRACE_HEAD 8          // floats per sequence before the attempt rows: d0, d1, d2, h0, first dt, 0, 0, 0
+#define LDP_TRACE_ROW 4           // per attempt: t, dt, ratio, accepted (1 / 0)
+
+// ---- Dormand-Prince 5(4), Shampine's variant as torchdiffeq 0.0.1 dopri5.py.  Rows 0 and 1 are the two evaluations of the
+// initial-step selection (z0 itself; z0 + h0 f0), rows 2..7 the six new stages of an attempt (the last one is y_new: FSAL).
+__constant__ float LDP_BETA[8][6] = {
+    {0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
+    {1.f, 0.f, 0.f, 0.f, 0.f, 0.f},
+    {(float)(1.0 / 5), 0.f, 0.f, 0.f, 0.f, 0.f},
+    {(float)(3.0 / 40), (float)(9.0 / 40), 0.f, 0.f, 0.f, 0.f},
+    {(float)(44.0 / 45), (float)(-56.0 / 15), (float)(32.0 / 9), 0.f, 0.f, 0.f},
+    {(float)(19372.0 / 6561), (float)(-25360.0 / 2187), (float)(64448.0 / 6561), (float)(-212.0 / 729), 0.f, 0.f},
+    {(float)(9017.0 / 3168), (float)(-355.0 / 33), (float)(46732.0 / 5247), (float)(49.0 / 176), (float)(-5103.0 / 18656), 0.f},
+    {(float)(35.0 / 384), 0.f, (float)(500.0 / 1113), (float)(125.0 / 192), (float)(-2187.0 / 6784), (float)(11.0 / 84)},
+};
+__constant__ float LDP_CERR[7] = {(float)(35.0 / 384 - 1951.0 / 21600), 0.f, (float)(500.0 / 1113 - 22642.0 / 50085), (float)(125.0 / 192 - 451.0 / 720),
+                                  (float)(-2187.0 / 6784 - -12231.0 / 42400), (float)(11.0 / 84 - 649.0 / 6300), (float)(-1.0 / 60.0)};
+__constant__ float LDP_CMID[7] = {(float)(6025192743.0 / 30085553152.0 / 2), 0.f, (float)(51252292925.0 / 65400821598.0 / 2),
+                                  (float)(-2691868925.0 / 45128329728.0 / 2), (float)(187940372067.0 / 1594534317056.0 / 2),
+                                  (float)(-1776094331.0 / 19743644256.0 / 2), (float)(11237099.0 / 235043384.0 / 2)};
+#define LDP_SAFETY 0.9f
+#define LDP_IFACTOR 10.0f
+#define LDP_DFACTOR 0.2f
+
+// out rows [16*rt0, 16*(rt0+nrt)) of W (packed, KC chunks) times the B-tile `in`; epilogue(rt, acc)   (lat_layer of ode.hip)
+template <int NRT, typename Epi>
+__device__ __forceinline__ void ldp_layer(const float *__restrict__ wp, int KC, int rt0, const float *in, int lane, Epi epi)
+{
+    // One CU streams the whole weight set from L2 every evaluation: keep 4 chunks (4 x NRT KiB per wave,
+    // 128 KiB per workgroup) of A fragments in flight in a register ring to cover the L2 latency.
+    const int g = lane >> 4, j = lane & 15;
+    f32x4 acc[NRT];
+#pragma unroll
+    for (int i = 0; i < NRT; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const float *wb = wp + ((long)rt0 * KC) * 256 + lane * 4;
+    f32x4 ring[4][NRT];
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int i = 0; i < NRT; ++i) ring[s][i] = ld4(wb + ((long)i * KC + (s < KC ? s : 0)) * 256);
+    for (int kc0 = 0; kc0 < KC; kc0 += 4) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int kc = kc0 + s;
+            if (kc < KC) {
+                const f32x4 bf = ld4(in + btile_off(kc * 4 + g, j, LDP_NCOL));
+#pragma unroll
+                for (int i = 0; i < NRT; ++i) {
+                    const f32x4 af = ring[s][i];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) acc[i] = mfma16(af[q], bf[q], acc[i]);
+                }
+                const int kn = (kc + 4 < KC) ? kc + 4 : kc;
+#pragma unroll
+                for (int i = 0; i < NRT; ++i) ring[s][i] = ld4(wb + ((long)i * KC + kn) * 256);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NRT; ++i) epi(rt0 + i, acc[i]);
+}
+
+// sum over the 64 lanes in one fixed order; every lane returns the same bits (a + b == b + a)
+__device__ __forceinline__ double ldp_wave_sum(double v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(512) void latent_dp5_kernel(const float *__restrict__ z0, int ldz, const float *__restrict__ times,
+                                                         int B, int Tu, int D, int H, float rtol, float atol, int max_attempts,
+                                                         const float *__restrict__ w0p, const float *__restrict__ b0,
+                                                         const float *__restrict__ w1p, const float *__restrict__ b1,
+                                                         const float *__restrict__ w2p, const float *__restrict__ b2,
+                                                         const float *__restrict__ w3p, const float *__restrict__ b3,
+                                                         float *__restrict__ out, float *__restrict__ trace, int *__restrict__ counters)
+{
+    // B-tiles: stage input (64 x 16, padded to 32 k-rows of 4), two hidden buffers (512 x 16)
+    __shared__ __attribute__((aligned(16))) float s_in[16 * LDP_NCOL * 4];
+    __shared__ __attribute__((aligned(16))) float s_h1[128 * LDP_NCOL * 4], s_h2[128 * LDP_NCOL * 4];
+    __shared__ float s_z[LDP_EL], s_yn[LDP_EL], s_k[7][LDP_EL];      // state, y_new, k1..k7; element (d, c) at d * 16 + c
+    __shared__ float s_dt[LDP_NCOL];                                  // the step of the next evaluations, per column (0: masked)
+    __shared__ int s_done[LDP_NCOL];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g = lane >> 4, j = lane & 15;
+    const int b0i = blockIdx.x * LDP_NCOL;
+    const int KC0 = 2 * ((D + 31) / 32), KCH = 2 * ((H + 31) / 32);
+    const int RTH = (H + 15) / 16, RTD = (D + 15) / 16;
+
+    for (int i = tid; i < LDP_EL; i += 512) {
+        const int d = i / LDP_NCOL, c = i % LDP_NCOL;
+        s_z[i] = (d < D && b0i + c < B) ? z0[(long)(b0i + c) * ldz + d] : 0.f;
+        s_yn[i] = 0.f;
+#pragma unroll
+        for (int q = 0; q < 7; ++q) s_k[q][i] = 0.f;
+    }
+    for (int i = tid; i < 16 * LDP_NCOL * 4; i += 512) s_in[i] = 0.f;   // K padding rows stay zero
+    for (int i = tid; i < 128 * LDP_NCOL * 4; i += 512) { s_h1[i] = 0.f; s_h2[i] = 0.f; }
+    if (tid < LDP_NCOL) { s_dt[tid] = 0.f; s_done[tid] = b0i + tid < B ? 0 : 1; }
+    __syncthreads();
+
+    // s_in = z + dt_c * sum_q LDP_BETA[row][q] k_{q+1} as a B-tile (row d, col c); row 7 is y_new: kept
+    auto write_in = [&](int row) {
+        for (int i = tid; i < LDP_EL; i += 512) {
+            const int d = i / LDP_NCOL, c = i % LDP_NCOL;
+            if (d < D) {
+                float acc = 0.f;
+                for (int q = 0; q + 2 <= row && q < 6; ++q) {
+                    const float bq = LDP_BETA[row][q];
+                    if (bq != 0.f) acc += bq * s_k[q][i];
+                }
+                if (row == 1) acc = s_k[0][i];
+                const float v = s_z[i] + s_dt[c] * acc;
+                s_in[btile_off(d >> 2, c, LDP_NCOL) + (d & 3)] = v;
+                if (row == 7) s_yn[i] = v;
+            }
+        }
+    };
+    auto dyn = [&](float *kout) {  // s_in -> kout ; latent_ode_model.py:139-147 (Linear-Tanh x3, Linear)
+        __syncthreads();
+        for (int rt = wave * 4; rt < RTH; rt += 32)
+            ldp_layer<4>(w0p, KC0, rt, s_in, lane, [&](int r, f32x4 a) {
+                const f32x4 bb = ld4(b0 + r * 16 + 4 * g);
+                f32x4 v;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = tanhf(a[q] + bb[q]);
+                st4(s_h1 + btile_off(r * 4 + g, j, LDP_NCOL), v);
+            });
+        __syncthreads();
+        for (int rt = wave * 4; rt < RTH; rt += 32)
+            ldp_layer<4>(w1p, KCH, rt, s_h1, lane, [&](int r, f32x4 a) {
+                const f32x4 bb = ld4(b1 + r * 16 + 4 * g);
+                f32x4 v;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = tanhf(a[q] + bb[q]);
+                st4(s_h2 + btile_off(r * 4 + g, j, LDP_NCOL), v);
+            });
+        __syncthreads();
+        for (int rt = wave * 4; rt < RTH; rt += 32)
+            ldp_layer<4>(w2p, KCH, rt, s_h2, lane, [&](int r, f32x4 a) {
+                const f32x4 bb = ld4(b2 + r * 16 + 4 * g);
+                f32x4 v;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = tanhf(a[q] + bb[q]);
+                st4(s_h1 + btile_off(r * 4 + g, j, LDP_NCOL), v);
+            });
+        __syncthreads();
+        if (wave < RTD)
+            ldp_layer<1>(w3p, KCH, wave, s_h1, lane, [&](int r, f32x4 a) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int d = r * 16 + 4 * g + q;
+                    if (d < D) kout[d * LDP_NCOL + j] = a[q] + b3[d];
+                }
+            });
+        __syncthreads();
+    };
+
+    // ---- the control state of this wave's two columns (wave-uniform), lane = component d
+    const bool dv = lane < D;
+    const int ei[2] = {lane * LDP_NCOL + 2 * wave, lane * LDP_NCOL + 2 * wave + 1};   // this lane's element of either column
+    const float t_first = times[0];
+    const double dD = (double)D;
+    double tc[2] = {0.0, 0.0};                       // solver time, relative to times[0]
+    float dtc[2] = {0.f, 0.f}, h0c[2] = {0.f, 0.f}, d0c[2] = {0.f, 0.f}, d1c[2] = {0.f, 0.f};
+    int cur[2] = {0, 0}, nacc[2] = {0, 0}, nrej[2] = {0, 0};
+    bool fin[2], valid[2];
+#pragma unroll
+    for (int cc = 0; cc < 2; ++cc) { valid[cc] = b0i + 2 * wave + cc < B; fin[cc] = !valid[cc]; }
+
+    // the stamps of column cc up to time t1 (inclusive) from the interpolant p(x) = (((A x + B) x + C) x + Dc) x + y0 of the
+    // step [t0, t1] (lin == false: every stamp takes y1 -- the rows at times[0])
+    auto emit = [&](int cc, double t0, double t1, bool lin, double A, double Bc, double C, double Dc, float y0, float y1) {
+        float *orow = out + (long)(b0i + 2 * wave + cc) * Tu * D;
+        int c1 = cur[cc];
+        while (c1 < Tu) {                            // the stamps are ascending: the ones <= t1 are a prefix of the rest
+            const int i = c1 + lane;
+            const bool le = i < Tu && (double)(times[i] - t_first) <= t1;
+            const unsigned long long m = __ballot(le);
+            const int n = m == ~0ull ? 64 : __builtin_ctzll(~m);
+            c1 += n;
+            if (n < 64) break;
+        }
+        for (int i = cur[cc]; i < c1; ++i) {
+            const double tn = (double)(times[i] - t_first);     // latent_ode_model.py:58
+            double v = (double)y1;
+            if (lin && tn != t1) {
+                const double xx = (tn - t0) / (t1 - t0);
+                v = (((A * xx + Bc) * xx + C) * xx + Dc) * xx + (double)y0;
+            }
+            if (dv) orow[(long)i * D + lane] = (float)v;
+        }
+        cur[cc] = c1;
+    };
+
+    // ---- _select_initial_step(order = 4): f0 = f(z0); d0, d1; h0; f1 = f(z0 + h0 f0); d2; first dt
+    write_in(0);
+    dyn(s_k[0]);
+#pragma unroll
+    for (int cc = 0; cc < 2; ++cc) {
+        if (!valid[cc]) continue;
+        const float z = s_z[ei[cc]], f0 = s_k[0][ei[cc]];
+        const float sc = atol + fabsf(z) * rtol;
+        const float a = z / sc, b = f0 / sc;
+        const double S0 = ldp_wave_sum(dv ? (double)a * (double)a : 0.0), S1 = ldp_wave_sum(dv ? (double)b * (double)b : 0.0);
+        const double d0 = sqrt(S0 / dD), d1 = sqrt(S1 / dD);
+        const double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * (d0 / fmax(d1, 1e-300));
+        d0c[cc] = (float)d0;
+        d1c[cc] = (float)d1;
+        h0c[cc] = (float)h0;
+        if (lane == 0) s_dt[2 * wave + cc] = h0c[cc];
+    }
+    __syncthreads();
+    write_in(1);
+    dyn(s_k[1]);
+#pragma unroll
+    for (int cc = 0; cc < 2; ++cc) {
+        if (!valid[cc]) continue;
+        const int c = 2 * wave + cc;
+        const float z = s_z[ei[cc]], f0 = s_k[0][ei[cc]], f1 = s_k[1][ei[cc]];
+        const float sc = atol + fabsf(z) * rtol;
+        const float a = (f1 - f0) / sc;
+        const double S = ldp_wave_sum(dv ? (double)a * (double)a : 0.0);
+        const float d2 = (float)(sqrt(S / dD) / (double)h0c[cc]);
+        const float h1 = (d1c[cc] <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0c[cc] * 1e-3f) : powf(0.01f / fmaxf(d1c[cc], d2), 0.2f);
+        dtc[cc] = fminf(100.f * h0c[cc], h1);
+        if (trace && lane < LDP_TRACE_HEAD) {
+            const float hd[LDP_TRACE_HEAD] = {d0c[cc], d1c[cc], d2, h0c[cc], dtc[cc], 0.f, 0.f, 0.f};
+            float v = 0.f;
+#pragma unroll
+            for (int q = 0; q < LDP_TRACE_HEAD; ++q) v = lane == q ? hd[q] : v;
+            trace[(long)(b0i + c) * (LDP_TRACE_HEAD + LDP_TRACE_ROW * max_attempts) + lane] = v;
+        }
+        emit(cc, 0.0, 0.0, false, 0.0, 0.0, 0.0, 0.0, z, z);          // the stamps equal to times[0]: z0
+        fin[cc] = cur[cc] >= Tu;
+        if (lane == 0) { s_dt[c] = fin[cc] ? 0.f : dtc[cc]; s_done[c] = fin[cc] ? 1 : 0; }
+    }
+    // masked columns (padding) keep s_dt = 0 from here on
+    if (lane == 0)
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc)
+            if (!valid[cc]) s_dt[2 * wave + cc] = 0.f;
+
+    // ---- the attempts
+    for (int att = 0;; ++att) {
+        __syncthreads();
+        int all = 1;
+#pragma unroll
+        for (int c = 0; c < LDP_NCOL; ++c) all &= s_done[c];
+        if (all || att >= max_attempts) break;                           // workgroup-uniform: s_done is read behind the barrier
+#pragma unroll 1
+        for (int row = 2; row < 8; ++row) {
+            write_in(row);
+            dyn(s_k[row - 1]);
+        }
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc) {
+            if (fin[cc]) continue;
+            const int c = 2 * wave + cc, e = ei[cc];
+            const float dt = dtc[cc];
+            const float z = s_z[e], yn = s_yn[e];
+            float kk[7];
+#pragma unroll
+            for (int q = 0; q < 7; ++q) kk[q] = s_k[q][e];
+            float es = 0.f, ms = 0.f;
+#pragma unroll
+            for (int q = 0; q < 7; ++q) {
+                if (LDP_CERR[q] != 0.f) es += LDP_CERR[q] * kk[q];
+                if (LDP_CMID[q] != 0.f) ms += LDP_CMID[q] * kk[q];
+            }
+            const float err = dt * es;
+            const float tol = atol + rtol * fmaxf(fabsf(z), fabsf(yn));
+            const float qe = err / tol;
+            const float r = (float)(ldp_wave_sum(dv ? (double)qe * (double)qe : 0.0) / dD);     // mean((err / tol)^2)
+            const bool accept = r <= 1.f;
+            float dt_next;
+            if (r == 0.f) dt_next = dt * LDP_IFACTOR;
+            else {
+                const float inv_d = r < 1.f ? 1.f : 1.f / LDP_DFACTOR;
+                const float factor = fmaxf(1.f / LDP_IFACTOR, fminf(powf(sqrtf(r), 0.2f) / LDP_SAFETY, inv_d));
+                dt_next = dt / factor;
+            }
+            if (trace && lane < LDP_TRACE_ROW) {
+                const float v = lane == 0 ? (float)tc[cc] : lane == 1 ? dt : lane == 2 ? r : (accept ? 1.f : 0.f);
+                trace[(long)(b0i + c) * (LDP_TRACE_HEAD + LDP_TRACE_ROW * max_attempts) + LDP_TRACE_HEAD + LDP_TRACE_ROW * att + lane] = v;
+            }
+            if (accept) {
+                ++nacc[cc];
+                const double t0 = tc[cc], t1 = tc[cc] + (double)dt;
+                const float ymid = z + dt * ms;
+                const double y0d = z, y1d = yn, ymd = ymid, fa = kk[0], fb = kk[6], h = dt;
+                const double A = 2.0 * h * (fb - fa) - 8.0 * (y1d + y0d) + 16.0 * ymd;
+                const double Bc = h * (5.0 * fa - 3.0 * fb) + 18.0 * y0d + 14.0 * y1d - 32.0 * ymd;
+                const double C = h * (fb - 4.0 * fa) - 11.0 * y0d - 5.0 * y1d + 16.0 * ymd;
+                emit(cc, t0, t1, true, A, Bc, C, h * fa, z, yn);
+                tc[cc] = t1;
+                if (dv) { s_z[e] = yn; s_k[0][e] = kk[6]; }              // commit; FSAL
+                fin[cc] = cur[cc] >= Tu;
+            } else
+                ++nrej[cc];
+            dtc[cc] = dt_next;
+            if (lane == 0) { s_dt[c] = fin[cc] ? 0.f : dt_next; s_done[c] = fin[cc] ? 1 : 0; }
+        }
+    }
+
+    // ---- counters; NaN in the rows a sequence did not reach; zero in the trace rows it did not use
+#pragma unroll
+    for (int cc = 0; cc < 2; ++cc) {
+        if (!valid[cc]) continue;
+        const long b = b0i + 2 * wave + cc;
+        const int na = nacc[cc] + nrej[cc];
+        if (lane < 4) counters[b * 4 + lane] = lane == 0 ? nacc[cc] : lane == 1 ? nrej[cc] : lane == 2 ? 2 + 6 * na : (fin[cc] ? 1 : 0);
+        if (dv)
+            for (int i = cur[cc]; i < Tu; ++i) out[(b * Tu + i) * D + lane] = __builtin_nanf("");
+        if (trace) {
+            float *tr = trace + b * (LDP_TRACE_HEAD + LDP_TRACE_ROW * max_attempts) + LDP_TRACE_HEAD;
+            for (long i = (long)LDP_TRACE_ROW * na + lane; i < (long)LDP_TRACE_ROW * max_attempts; i += 64) tr[i] = 0.f;
+        }
+    }
+}
+
+extern "C" int caspr_latent_dopri5_f32(const float *z0, int ldz, const float *times, int B, int Tu, int D, int H,
+                                       float rtol, float atol, int max_attempts, const float *w0p, const float *b0,
+                                       const float *w1p, const float *b1, const float *w2p, const float *b2,
+                                       const float *w3p, const float *b3, float *out, float *trace, int32_t *counters,
+                                       void *stream)
+{
+    CASPR_REQUIRE(z0 && times && out && counters && w0p && w1p && w2p && w3p && b0 && b1 && b2 && b3, "latent_dopri5: null pointer");
+    CASPR_REQUIRE(B > 0 && Tu > 0 && max_attempts > 0 && D > 0 && H > 0 && ldz >= D, "latent_dopri5: bad sizes B=%d Tu=%d D=%d H=%d ldz=%d max_attempts=%d",
+                  B, Tu, D, H, ldz, max_attempts);
+    CASPR_REQUIRE(rtol > 0.f && atol > 0.f && isfinite(rtol) && isfinite(atol), "latent_dopri5: rtol and atol must be positive and finite");
+    if (!(D <= 64 && H <= 512 && H % 64 == 0)) {
+        caspr_set_error("latent_dopri5: unsupported sizes D=%d H=%d (need D<=64, H<=512, H %% 64 == 0)", D, H);
+        return CASPR_EUNSUP;
+    }
+    latent_dp5_kernel<<<dim3(ceil_div(B, LDP_NCOL)), dim3(512), 0, (hipStream_t)stream>>>(z0, ldz, times, B, Tu, D, H, rtol, atol, max_attempts,
+                                                                                         w0p, b0, w1p, b1, w2p, b2, w3p, b3, out, trace,
+                                                                                         (int *)counters);
+    CASPR_CHECK_LAUNCH("latent_dopri5");
+    return CASPR_OK;
+}

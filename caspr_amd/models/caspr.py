@@ -43,6 +43,8 @@ class _EarlyLatent:
         return bool(ops.LATENT_TEAM and EARLY_LATENT_TEAM)
 
     def reserve_cus(self, B):
+        if self.latent_ode.method == "dopri5":
+            return (B + 15) // 16          # the adaptive solve is single-workgroup: one unit per 16 sequences
         return (32 if self.team() else 1) * ((B + 15) // 16)
 
     def __call__(self, z0_partial):
@@ -50,14 +52,21 @@ class _EarlyLatent:
         self.stream.wait_stream(main)
         with torch.cuda.stream(self.stream):
             z_init = z0_partial[:, :self.channels]
-            out = ops.latent_rk4(z_init, self.plan["sorted_t"], self.latent_ode.rk4_steps, self.latent_ode._weights(), team=self.team())
+            if self.latent_ode.method == "dopri5":
+                # one launch, the step control on the device: nothing here waits on the host (the measured count is installed by solve_dopri5)
+                out = self.latent_ode.solve_dopri5(z_init, self.plan["sorted_t"])
+            else:
+                out = ops.latent_rk4(z_init, self.plan["sorted_t"], self.latent_ode.rk4_steps, self.latent_ode._weights(), team=self.team())
             # what aggregate_and_solve_latent does with the solution, here too: off the path between the encoder's last kernel and the flow
             self.out = out[self.plan["rows"], self.plan["pos"], :]                      # (B, T, H): the requested stamps
-            self.latent_ode.ode_func._num_evals.mul_(0).add_(self.plan["evals"])        # evaluations actually run (an element-wise op, not a blit)
+            if self.latent_ode.method != "dopri5":
+                self.latent_ode.ode_func._num_evals.mul_(0).add_(self.plan["evals"])    # evaluations actually run (an element-wise op, not a blit)
             self.event = torch.cuda.Event()
             self.event.record()
         z0_partial.record_stream(self.stream)
         self.out.record_stream(main)
+        if self.latent_ode.method == "dopri5":
+            self.latent_ode.last_nfe_per_sequence.record_stream(main)
 
 
 # the latent solve beside the encoder's last layer (config.early_latent = False: in front of the flow, as in rounds 1-3)
@@ -135,7 +144,8 @@ class CaSPR(nn.Module):
     def __init__(self, radii_list=[0.02, 0.05, 0.1, 0.2, 0.4, 0.8], local_feat_size=512, latent_feat_size=1600,
                  ode_hidden_size=512, motion_feat_size=64, pretrain_tnocs=False, augment_quad=True, augment_pairs=True,
                  cnf_blocks=1, regress_tnocs=True, *, cnf_rk4_steps=8, latent_rk4_steps=2, check_tol=1e-5, latent_check_tol=None,
-                 check_action="warn", check_points=64, cnf_method="rk4", cnf_atol=1e-5, cnf_rtol=1e-5):
+                 check_action="warn", check_points=64, cnf_method="rk4", cnf_atol=1e-5, cnf_rtol=1e-5,
+                 latent_method="rk4", latent_rtol=1e-3, latent_atol=1e-3):
         super(CaSPR, self).__init__()
         # Run-time accuracy guard of the fixed-step integrators: ON by default at the reference's own tolerances, reporting as a
         # RuntimeWarning (check_action="raise": CasprAccuracyError; check_tol=None: off).  The reference's dopri5 controls its error at every
@@ -162,8 +172,10 @@ class CaSPR(nn.Module):
                                   tnocs_point_size=self.tnocs_point_size, regress_tnocs=self.regress_tnocs)
         if self.pretrain_tnocs:
             return
+        # latent_method="dopri5": the latent ODE integrates to latent_rtol / latent_atol (the reference's 1e-3) with the adaptive kernel
+        # (inference only; per-sequence error control); the guard and calibrate_rk4_steps skip it, as they skip a dopri5 block
         self.latent_ode = LatentODE(input_size=self.motion_feat_size, hidden_size=ode_hidden_size, num_layers=2,
-                                    nonlinearity=nn.Tanh, rk4_steps=latent_rk4_steps)
+                                    nonlinearity=nn.Tanh, rk4_steps=latent_rk4_steps, method=latent_method, rtol=latent_rtol, atol=latent_atol)
         self.cnf_args = PointCNFArgs()
         self.cnf_args.zdim = latent_feat_size
         self.cnf_args.num_blocks = cnf_blocks
@@ -284,6 +296,8 @@ class CaSPR(nn.Module):
         """The latent solve once more at half (or twice) the steps per interval, on the single-workgroup kernel (one compute unit,
         no co-residency requirement: it may run beside anything) on the guard stream; max |z_L - z_L'| over the requested stamps
         goes to the deferred channel (ops.guard_track).  Nothing on the current stream waits for it."""
+        if self.latent_ode.method == "dopri5":
+            return                # the adaptive solve controls its own error: no step count to halve, no check solve
         L = self.latent_ode.rk4_steps
         L2, factor = _other_steps(L)
         tol = self.latent_check_tol if self.latent_check_tol is not None else 100.0 * self.check_tol
@@ -534,7 +548,7 @@ class CaSPR(nn.Module):
             z0, _ = self.encode(xs)
             times = xs[:, :, 0, 3] / max_timestamp if timestamps is None else timestamps.view(1, -1).repeat(xs.shape[0], 1).to(xs)
             lat = None
-            if latent_tol is not None:
+            if latent_tol is not None and self.latent_ode.method == "rk4":        # a dopri5 latent ODE has no step count: left alone
                 zs = {}
 
                 def zsol(L):

@@ -3,7 +3,8 @@
 Same parameter tree, including the reference's double registration of the dynamics net under
 `ode_func.*` and `solver.ode_func.*` (latent_ode_model.py:36-38,81) and the `_num_evals` buffer.
 DEVIATION (documented): the reference integrates with adaptive dopri5 at rtol=atol=1e-3
-(latent_ode_model.py:38,83); this build runs `steps` RK4 steps per requested interval.
+(latent_ode_model.py:38,83); this build runs `steps` RK4 steps per requested interval by default.  method="dopri5" integrates
+to rtol / atol with the adaptive kernel instead (ops.latent_dopri5: inference only, error control per sequence).
 """
 import torch
 import torch.nn as nn
@@ -13,8 +14,11 @@ from ..utils.weight_cache import WeightCache
 
 
 class LatentODE(nn.Module):
-    def __init__(self, input_size=1024, hidden_size=1024, num_layers=2, nonlinearity=nn.Tanh, augment_size=0, rk4_steps=2):
+    def __init__(self, input_size=1024, hidden_size=1024, num_layers=2, nonlinearity=nn.Tanh, augment_size=0, rk4_steps=2,
+                 method="rk4", rtol=1e-3, atol=1e-3, max_attempts=1000):
         super(LatentODE, self).__init__()
+        if method not in ("rk4", "dopri5"):
+            raise ValueError("LatentODE method must be 'rk4' or 'dopri5', got %r" % (method,))
         if nonlinearity is not nn.Tanh or num_layers != 2:
             raise ValueError("the latent RK4 kernel implements the reference configuration: 2 hidden layers, Tanh (caspr.py:61-64)")
         if augment_size != 0:
@@ -23,6 +27,10 @@ class LatentODE(nn.Module):
         self.augment_size = augment_size
         self.output_size = input_size + self.augment_size
         self.rk4_steps = rk4_steps
+        self.method = method          # "dopri5": forward / solve_at integrate to rtol / atol (inference only)
+        self.rtol, self.atol = rtol, atol
+        self.max_attempts = max_attempts
+        self.last_nfe_per_sequence = None    # dopri5: (B,) int32 device tensor of the last solve
         self.ode_func = DynamicsNet(input_size=self.output_size, hidden_size=hidden_size, num_layers=num_layers, nonlinearity=nonlinearity)
         self.solver = ODESolver(self.ode_func, method='dopri5', rtol=1e-3, atol=1e-4)
         init_network_weights(self.ode_func)
@@ -49,12 +57,25 @@ class LatentODE(nn.Module):
         if z0.shape[1] != self.input_size:
             raise ValueError("expected %d latent dims, got %d" % (self.input_size, z0.shape[1]))
         if torch.is_grad_enabled() and (z0.requires_grad or any(p.requires_grad for p in self.ode_func.parameters())):
+            if self.method == "dopri5":
+                raise ValueError("LatentODE(method='dopri5') is an inference option: no gradient through the adaptive solve (training keeps RK4)")
             from ..train.flow_grad import latent_solve_train                                    # differentiable RK4 (training)
             return latent_solve_train(self, z0, t)
+        if self.method == "dopri5":
+            return self.solve_dopri5(z0, t.detach().float().contiguous())
         # z0 may be the view z[:, :H] of the (B,1600) encoder output: the kernel takes its row stride
         out = ops.latent_rk4(z0, t.detach().float().contiguous(), self.rk4_steps, self._weights())
         Tu = t.shape[0]
         self.ode_func._num_evals += 4 * self.rk4_steps * max(Tu - 1, 0)
+        return out
+
+    def solve_dopri5(self, z0, sorted_t, rtol=None, atol=None):
+        """The adaptive solve at the ascending stamps sorted_t (Tu,) -> (B,Tu,H).  The evaluation count is MEASURED: the kernel's
+        counters, their maximum over the sequences installed on the device (no host read)."""
+        out, info = ops.latent_dopri5(z0, sorted_t, self.rtol if rtol is None else rtol, self.atol if atol is None else atol, self._weights(),
+                                      max_attempts=self.max_attempts, return_trace=True)
+        self.last_nfe_per_sequence = info["nfe"]
+        self.ode_func._num_evals.mul_(0).add_(info["nfe"].max().to(self.ode_func._num_evals.dtype))      # element-wise ops, no .item()
         return out
 
     def plan_times(self, time_tensor):
@@ -79,6 +100,10 @@ class LatentODE(nn.Module):
         plan: plan_times(time_tensor) made earlier on this stream."""
         if plan is None or plan["shape"] != tuple(time_tensor.shape):
             plan = self.plan_times(time_tensor)
+        if self.method == "dopri5":
+            if torch.is_grad_enabled() and z0.requires_grad:
+                raise ValueError("LatentODE(method='dopri5') is an inference option: no gradient through the adaptive solve (training keeps RK4)")
+            return self.solve_dopri5(z0, plan["sorted_t"])[plan["rows"], plan["pos"], :]
         out = ops.latent_rk4(z0, plan["sorted_t"], self.rk4_steps, self._weights())            # (B, B*T, H)
         self.ode_func._num_evals.copy_(plan["evals"])                                           # evaluations actually run
         return out[plan["rows"], plan["pos"], :]
@@ -96,12 +121,31 @@ class ODESolver(nn.Module):
         self.ode_func = ode_func
         self.rtol = rtol
         self.atol = rtol   # sic: the reference assigns rtol (latent_ode_model.py:83)
+        self._cache = WeightCache()
         if not isinstance(self.ode_func, nn.Module):
             raise ValueError('ode_func is required to be an instance of nn.Module to use the adjoint method')
 
+    def _weights(self):
+        lin = [self.ode_func.dynamics_net[i] for i in (0, 2, 4, 6)]
+
+        def build():
+            out = []
+            for l in lin:
+                out += [ops.PackedWeight(l.weight.detach().contiguous()), l.bias.detach().contiguous()]
+            return out
+        return self._cache.get("w", [l.weight for l in lin] + [l.bias for l in lin], build)
+
     def forward(self, z0, t):
-        raise NotImplementedError("the adaptive solver is replaced by LatentODE's RK4 kernel; call LatentODE.forward "
-                                  "(the GPU dopri5 option, CaSPR(cnf_method='dopri5'), covers the point CNF only: the latent ODE stays RK4)")
+        """z0 (B,H), t (T,) ascending -> (T,B,H) as the reference's odeint call returns it (latent_ode_model.py:85-99), integrated by
+        the adaptive kernel at this solver's own rtol / atol (inference only)."""
+        if self.method != "dopri5":
+            raise ValueError("ODESolver: the GPU solver is dopri5, got method %r" % (self.method,))
+        if not z0.is_cuda:
+            raise ValueError("caspr_amd.ODESolver runs on the GPU only (HIP kernels)")
+        if torch.is_grad_enabled() and (z0.requires_grad or any(p.requires_grad for p in self.ode_func.parameters())):
+            raise ValueError("ODESolver: no gradient through the adaptive solve (training keeps RK4: LatentODE.forward)")
+        out = ops.latent_dopri5(z0, t.detach().float().contiguous(), self.rtol, self.atol, self._weights())
+        return out.permute(1, 0, 2)
 
 
 class DynamicsNet(nn.Module):

@@ -738,11 +738,14 @@ def _team_raise_if_failed(key, wait=False):
 
 
 def check_deferred_errors(wait=True):
-    """Raise CasprHipError if an earlier asynchronous kernel reported a failure (the latent team kernel's barrier), or
+    """Raise CasprHipError if an earlier asynchronous kernel reported a failure (the latent team kernel's barrier, the adaptive
+    latent solve's attempt budget), or
     CasprAccuracyError / warn if a run-time accuracy check of the fixed-step integrators came back above its tolerance
     (guard_track).  wait=True blocks until the status words of every outstanding solve / check have arrived."""
     for key in list(_team_status):
         _team_raise_if_failed(key, wait=wait)
+    for key in list(_dp5_status):
+        _dp5_raise_if_failed(key, wait=wait)
     _guard_drain(wait=wait)
 
 
@@ -867,6 +870,92 @@ def latent_rk4(z0, times, steps, wts, team=None):
         _lib.check(L.caspr_latent_rk4_f32(_p(z0), z0.stride(0), _p(times), B, Tu, D, H, int(steps), *ptrs, _p(out), _stream()), "caspr_latent_rk4_f32")
     return out
 
+
+LATENT_DP5_TRACE_HEAD, LATENT_DP5_TRACE_ROW = 8, 4      # include/caspr_hip.h: the trace layout of caspr_latent_dopri5_f32
+# The adaptive latent solve reports a used-up attempt budget through its `finished` words: copied to pinned memory behind the
+# launch and read when the copy has arrived (the team kernel's channel: the next solve on the stream, or check_deferred_errors).
+_dp5_status = {}         # stream key -> [(pinned host tensor, event, max_attempts)], oldest first
+_dp5_pool = []
+
+
+def _dp5_raise_if_failed(key, wait=False):
+    ring = _dp5_status.get(key)
+    failed = None
+    while ring:
+        host, ev, budget = ring[0]
+        if wait:
+            ev.synchronize()
+        if not ev.query():
+            break
+        ring.pop(0)
+        if int(host.min()) == 0 and failed is None:
+            failed = (int((host == 0).sum()), host.numel(), budget)
+        _dp5_pool.append(host)
+    if failed:
+        raise _lib.CasprHipError("caspr_latent_dopri5_f32 (code %d, CASPR_ENOCONV): %d of %d sequences had not reached the last time stamp after "
+                                 "max_attempts = %d attempts; the rows of the stamps they did not reach hold NaN.  Raise max_attempts or the "
+                                 "tolerance" % (-4, failed[0], failed[1], failed[2]))
+
+
+def _dp5_track(key, finished, max_attempts):
+    ring = _dp5_status.setdefault(key, [])
+    if len(ring) >= 64:                              # nobody drained for 64 solves: bound the backlog (blocks on the oldest)
+        ring[0][1].synchronize()
+        _dp5_raise_if_failed(key)
+    n = finished.numel()
+    slot = next((i for i, h in enumerate(_dp5_pool) if h.numel() == n), None)
+    host = _dp5_pool.pop(slot) if slot is not None else torch.ones(n, dtype=torch.int32).pin_memory()
+    ev = torch.cuda.Event()
+    host.copy_(finished, non_blocking=True)
+    ev.record(torch.cuda.current_stream())
+    ring.append((host, ev, max_attempts))
+
+
+def latent_dopri5(z0, times, rtol, atol, wts, max_attempts=1000, return_trace=False):
+    """Adaptive Dormand-Prince 5(4) solve of the latent dynamics to a tolerance (latent_ode_model.py:45-70 as the reference runs it:
+    torchdiffeq's dopri5), error control PER SEQUENCE, the whole solve in one launch with the step control on the device
+    (csrc/ode_latent_dp5.hip).  z0, times, wts as latent_rk4; times ascending, repeats allowed.  -> (B,Tu,D); with return_trace a dict
+    is appended: "d0", "d1", "d2", "h0", "dt0" (B,), "attempts" (B, max_attempts, 4) rows [t, dt, ratio, accepted], "accepted",
+    "rejected", "nfe" (B,) int32 -- all on the device.
+    Never synchronises and runs under stream capture.  A sequence that has not reached the last stamp after max_attempts attempts
+    leaves NaN in the rows it did not reach; CasprHipError is raised by the next solve on the stream or by check_deferred_errors()
+    (not tracked under capture, as latent_rk4)."""
+    _chk_f32(times, *[w for w in wts[1::2]])
+    if not z0.is_cuda or z0.dtype != torch.float32 or z0.dim() != 2 or z0.stride(1) != 1:
+        raise ValueError("latent_dopri5: z0 must be a float32 GPU (B,D) tensor with unit column stride")
+    _on_current_device(z0)
+    B = z0.shape[0]
+    D, H = wts[0].cin, wts[0].cout
+    if z0.shape[1] != D:
+        raise ValueError("latent_dopri5: z0 has %d columns, the dynamics net expects %d" % (z0.shape[1], D))
+    if times.dim() != 1 or times.shape[0] < 1 or B < 1:
+        raise ValueError("latent_dopri5: times must be a non-empty (Tu,) tensor and z0 hold at least one sequence")
+    rtol, atol, max_attempts = float(rtol), float(atol), int(max_attempts)
+    if not (0 < rtol < float("inf") and 0 < atol < float("inf")):
+        raise ValueError("latent_dopri5: rtol and atol must be positive and finite, got %r / %r" % (rtol, atol))
+    if max_attempts < 1:
+        raise ValueError("latent_dopri5: max_attempts must be positive, got %d" % max_attempts)
+    if torch.is_grad_enabled() and (z0.requires_grad or times.requires_grad):
+        raise ValueError("latent_dopri5: no gradient through the adaptive solve (training keeps RK4)")
+    Tu = times.shape[0]
+    out = torch.empty(B, Tu, D, device=z0.device, dtype=torch.float32)
+    trace = torch.empty(B, LATENT_DP5_TRACE_HEAD + LATENT_DP5_TRACE_ROW * max_attempts, device=z0.device, dtype=torch.float32) if return_trace else None
+    counters = torch.empty(B, 4, device=z0.device, dtype=torch.int32)
+    ptrs = [_p(w.data) if isinstance(w, PackedWeight) else _p(w) for w in wts]
+    key = (z0.device.index, torch.cuda.current_stream().cuda_stream)
+    capturing = torch.cuda.is_current_stream_capturing()           # hipGraph capture: no event queries, no host copies
+    if not capturing:
+        _dp5_raise_if_failed(key)                                  # status of the previous solve on this stream, if it has arrived
+    with timed("latent_dopri5"):
+        _lib.check(_lib.load().caspr_latent_dopri5_f32(_p(z0), z0.stride(0), _p(times), B, Tu, D, H, rtol, atol, max_attempts, *ptrs, _p(out),
+                                                       _p(trace), _p(counters), _stream()), "caspr_latent_dopri5_f32")
+    if not capturing:
+        _dp5_track(key, counters[:, 3], max_attempts)
+    if return_trace:
+        return out, {"d0": trace[:, 0], "d1": trace[:, 1], "d2": trace[:, 2], "h0": trace[:, 3], "dt0": trace[:, 4],
+                     "attempts": trace[:, LATENT_DP5_TRACE_HEAD:].view(B, max_attempts, LATENT_DP5_TRACE_ROW),
+                     "accepted": counters[:, 0], "rejected": counters[:, 1], "nfe": counters[:, 2]}
+    return out
 
 
 def pack_cnf_x6(w):

@@ -32,7 +32,7 @@ extern "C" {
 #define CASPR_EINVAL (-1)   /* bad argument (shape / alignment / null pointer)         */
 #define CASPR_ELAUNCH (-2)  /* hipLaunchKernel / hipGetLastError reported a failure    */
 #define CASPR_EUNSUP (-3)   /* shape outside what the kernels are instantiated for     */
-#define CASPR_ENOCONV (-4)  /* an adaptive solve used up its attempt budget (caspr_cnf_dopri5_f32) */
+#define CASPR_ENOCONV (-4)  /* an adaptive solve used up its attempt budget (caspr_cnf_dopri5_f32; caspr_latent_dopri5_f32: `finished`) */
 
 const char *caspr_last_error_string(void);
 int caspr_abi_version(void);
@@ -280,7 +280,29 @@ int caspr_latent_rk4_f32(const float *z0, int ldz, const float *times, int B, in
                          const float *w2p, const float *b2, const float *w3p, const float *b3, float *out,
                          void *stream);
 
-/* Same solve spread over a team of 32 workgroups per 16 sequences that keep the weights resident in LDS and meet at
+/* The latent ODE integrated to a TOLERANCE in ONE launch: adaptive Dormand-Prince 5(4) as torchdiffeq 0.0.1's dopri5 runs it
+ * (what the reference calls at rtol = atol = 1e-3, latent_ode_model.py:38,83; oracle.model.dopri5_solve restates it: initial step
+ * from d0 / d1 / d2 / h0, six evaluations per attempt with FSAL, tol = atol + rtol max(|z0|, |z1|), ratio = mean((err / tol)^2),
+ * accept iff ratio <= 1, safety 0.9, growth cap 10, shrink cap 0.2, steps NOT clipped at the stamps: the 4th-order interpolant is
+ * evaluated there), with ONE difference: the norms are taken PER SEQUENCE (row of B), so a sequence's codes are what the reference
+ * computes when it is called on that sequence alone, bit for bit whatever batch surrounds it.  csrc/ode_latent_dp5.hip: the
+ * evaluation of caspr_latent_rk4_f32 (same limits on D and H, any B, one workgroup per 16 sequences), each sequence with its own
+ * t, dt and accept / reject history, the step control on the device.  Arguments as caspr_latent_rk4_f32 with `steps` replaced by
+ * rtol, atol, max_attempts; times ascending, repeats allowed (repeated stamps give bit-identical rows), plus
+ *   trace     (B, 8 + 4 max_attempts) f32 or NULL: [d0, d1, d2, h0, first dt, 0, 0, 0] then per attempt [t, dt, ratio, accepted]
+ *             (t relative to times[0]; rows past the last attempt are zeroed);
+ *   counters  (B, 4) int32: accepted, rejected, function evaluations (2 + 6 attempts), finished.
+ * Enqueues one launch and never synchronises or reads device memory: usable under stream capture.  A sequence that has not reached
+ * the last stamp after max_attempts attempts gets finished = 0 and NaN in the rows of the stamps it did not reach (the caller
+ * reads the counters when it chooses to: CASPR_ENOCONV is the host's name for that state).  CASPR_EINVAL for bad arguments,
+ * CASPR_EUNSUP for D > 64, H > 512 or H % 64 != 0.                                                                          */
+int caspr_latent_dopri5_f32(const float *z0, int ldz, const float *times, int B, int Tu, int D, int H,
+                            float rtol, float atol, int max_attempts, const float *w0p, const float *b0,
+                            const float *w1p, const float *b1, const float *w2p, const float *b2,
+                            const float *w3p, const float *b3, float *out, float *trace, int32_t *counters,
+                            void *stream);
+
+/* The fixed-step solve of caspr_latent_rk4_f32 spread over a team of 32 workgroups per 16 sequences that keep the weights resident in LDS and meet at
  * three team barriers per evaluation (see csrc/ode.hip): ~3x lower latency of this serial stage.  H must be 512 and
  * B <= 64 (the 32*ceil(B/16) workgroups have to be co-resident); results equal caspr_latent_rk4_f32 up to the
  * re-association of the layer sums.  ws >= caspr_latent_team_ws_bytes(B), 256-byte aligned.                    */
