@@ -30,6 +30,8 @@ class KernelConfig:
     train_latent_node: bool = True      # training: the latent solve as one autograd node (team tape + team adjoint)
     train_cnf_checkpoint: bool = False  # training: keep the CNF's state per RK4 step only, recompute the step in the backward pass
                                         # (63 GB -> ~1/8 of tape at the cfg-3 shard for one more forward of the block)
+    train_cnf_block_node: bool = False  # training: a CNF block as ONE autograd node (train/flow_grad.py: CnfBlockSolve): the forward in one launch
+                                        # that writes no layer product (csrc/ode_train_fwd.hip), the reverse sweep taping one evaluation at a time
 
 
 # environment name -> (field, parser); read only under CASPR_DEBUG=1
@@ -49,6 +51,7 @@ _ENV = {
     "CASPR_CNF_NODE": ("train_cnf_hidden_node", lambda v: v != "0"),
     "CASPR_LATENT_NODE": ("train_latent_node", lambda v: v != "0"),
     "CASPR_CNF_CHECKPOINT": ("train_cnf_checkpoint", lambda v: v != "0"),
+    "CASPR_CNF_BLOCK_NODE": ("train_cnf_block_node", lambda v: v != "0"),
 }
 
 

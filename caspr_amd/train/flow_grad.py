@@ -588,6 +588,7 @@ OUT_NODE = _cfg.train_cnf_out_node          # False: the output layer's epilogue
 HIDDEN_NODE = _cfg.train_cnf_hidden_node    # False: CnfLayer + CnfLayerOut
 LATENT_NODE = _cfg.train_latent_node        # False: the per-layer form
 CHECKPOINT_STEPS = _cfg.train_cnf_checkpoint   # True: the CNF's tape per RK4 step, recomputed in the backward pass (cnf_block_train)
+BLOCK_NODE = _cfg.train_cnf_block_node      # True: a CNF block as one autograd node (CnfBlockSolve) where the shape allows; wins over CHECKPOINT_STEPS
 
 
 def latent_solve_train(lat, z0, times):
@@ -608,6 +609,99 @@ def latent_solve_train(lat, z0, times):
 # ---------------------------------------------------------------------------------------------
 # point CNF block (cnf.py:70-128, odefunc.py:119-142, diffeq_layers.py:83-90)
 # ---------------------------------------------------------------------------------------------
+def _layer_views(v_lm, BT, widths):
+    """Layer-major 1-D tensor ([layer][frame][channel]) -> the per-layer (BT, C_l) views."""
+    outs, off = [], 0
+    for w in widths:
+        outs.append(v_lm[off:off + BT * w].view(BT, w))
+        off += BT * w
+    return outs
+
+
+def _cnf_eval_fused(wb, t, y, G_lm, Bb_lm, tg_lm, tb_lm, e_rows, BT, n, widths):
+    """One evaluation of the ODE function on the training kernels in the fused-layer row layout (blk = 32): the nodes `func` of
+    cnf_block_train runs by default.  wb = (w0, b0, ..., w3, b3); y (BT,n,3) -> a (BT,n,3), nd (BT,n,1)."""
+    w0, b0, w1, b1, w2, b2, w3, b3 = wb
+    parts = SplitLayers.apply(torch.sigmoid(G_lm + t * tg_lm), Bb_lm + t * tb_lm, BT, widths)
+    h = CnfIn.apply(y.reshape(BT * n, 3), e_rows, w0, b0, parts[0], parts[4], n, 32)
+    z = CnfHidden.apply(h, w1, b1, parts[1], parts[5], w2, b2, parts[2], parts[6], w3, n)
+    return CnfOut.apply(z, b3, parts[3], parts[7], e_rows, n, 32)
+
+
+class CnfBlockSolve(torch.autograd.Function):
+    """A CNF block's whole RK4 solve (forward direction, Hutchinson divergence for a given e) as ONE autograd node whose tape does not
+    grow with the layer width: forward = one launch of caspr_cnf_train_fwd_f32, which keeps every layer product on chip and writes only
+    the (BT,n,3) point state of each evaluation (stage input, stage outputs); backward = a hand-written reverse sweep over steps S-1..0
+    and stages 4..1 that rebuilds ONE evaluation's tape at a time from its stored stage input with the training kernels (SplitLayers ->
+    CnfIn -> CnfHidden -> CnfOut), back-propagates the stage cotangent through it, adds the result to preallocated gradient buffers in
+    a fixed order (stage-major within a step, steps descending: two runs give the same bits) and drops that tape.  The RK4 algebra
+    between the evaluations is done by hand, including dL/dt_end through the step size h = t_end / S and through the stage times.
+    Discretise-then-optimise, as the taped route: the gradient of the map the forward kernel integrates, up to the rounding between the
+    inference-class forward and the training kernels of the recomputation.
+    x (BT,n,3), logpx (BT,n,1), G_lm / Bb_lm / tg_lm / tb_lm layer-major as in cnf_block_train, t_end 0-dim tensor, e (BT,n,3),
+    w1x / w2x (ops.pack_cnf_x6), steps, widths, then w0, b0, ..., w3, b3 -> (x_T, logp_T)."""
+
+    @staticmethod
+    def forward(ctx, x, logpx, G_lm, Bb_lm, tg_lm, tb_lm, t_end, e, w1x, w2x, steps, widths, *wb):
+        BT, n, _ = x.shape
+        hyper = torch.cat(_layer_views(G_lm.detach(), BT, widths) + _layer_views(Bb_lm.detach(), BT, widths), dim=1).contiguous()
+        tcol = torch.cat([v[0] for v in _layer_views(tg_lm.detach(), BT, widths) + _layer_views(tb_lm.detach(), BT, widths)]).contiguous()
+        w0, b0, w1, b1, w2, b2, w3, b3 = [t_.detach().contiguous() for t_ in wb]
+        ec = e.detach().contiguous()
+        y, lp, ys, ka, knd = T.cnf_train_fwd(x.detach().contiguous(), logpx.detach().contiguous(), ec, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3,
+                                             t_end.detach().reshape(1).contiguous(), steps)
+        ctx.save_for_backward(ys, ka, knd, G_lm, Bb_lm, tg_lm, tb_lm, t_end, ec)
+        ctx.steps, ctx.widths, ctx.wb = steps, widths, wb
+        return y, lp
+
+    @staticmethod
+    def backward(ctx, gy, glp):
+        ys, ka, knd, G_lm, Bb_lm, tg_lm, tb_lm, t_end, e = ctx.saved_tensors
+        S, widths, wb = ctx.steps, ctx.widths, ctx.wb
+        _, _, BT, n, _ = ys.shape
+        dev = ys.device
+        gy = torch.zeros(BT, n, 3, device=dev, dtype=ys.dtype) if gy is None else gy.contiguous()
+        glp = torch.zeros(BT, n, 1, device=dev, dtype=ys.dtype) if glp is None else glp.contiguous()     # logp_{s+1} = logp_s + ...: the same cotangent at every step
+        h = (t_end.detach() / S).reshape(())
+        e_rows = e.reshape(BT * n, 3)
+        hyp = [v.detach().requires_grad_(True) for v in (G_lm, Bb_lm, tg_lm, tb_lm)]
+        wsel = [i for i, w in enumerate(wb) if w.requires_grad]
+        d_hyp = [torch.zeros_like(v) for v in hyp]
+        d_wb = [torch.zeros_like(w) if w.requires_grad else None for w in wb]
+        dh = torch.zeros((), device=dev, dtype=torch.float64)          # dL/dh, summed in f64 (a handful of dot products per evaluation)
+        dot = lambda u, v: (u.double() * v.double()).sum()
+        CW = (1.0 / 6.0, 2.0 / 6.0, 2.0 / 6.0, 1.0 / 6.0)              # weights of k1..k4 in the RK4 combination
+        TC = (0.0, 0.5, 0.5, 1.0)                                      # stage i: t + TC[i] h, input y + TC[i] h k_{i-1}
+        for s in range(S - 1, -1, -1):
+            k, nd = ka[s], knd[s]
+            dh += (dot(gy, k[0] + 2.0 * k[1] + 2.0 * k[2] + k[3]) + dot(glp, nd[0] + 2.0 * nd[1] + 2.0 * nd[2] + nd[3])) / 6.0
+            gy_next, g_in = gy.clone(), None                           # g_in: cotangent of the NEXT stage's input
+            for st in (3, 2, 1, 0):
+                ka_bar = (CW[st] * h) * gy
+                if g_in is not None:
+                    ka_bar = torch.addcmul(ka_bar, g_in, TC[st + 1] * h)
+                nd_bar = (CW[st] * h) * glp
+                with torch.enable_grad():
+                    t = (h * s + TC[st] * h).detach().requires_grad_(True)
+                    y_in = ys[s, st].detach().requires_grad_(True)
+                    a, nd_ = _cnf_eval_fused(wb, t, y_in, hyp[0], hyp[1], hyp[2], hyp[3], e_rows, BT, n, widths)
+                    g = torch.autograd.grad((a, nd_), [y_in, t] + hyp + [wb[i] for i in wsel], (ka_bar, nd_bar))
+                del a, nd_
+                g_in = g[0]
+                for buf, gi in zip(d_hyp, g[2:6]):
+                    buf.add_(gi)
+                for i, gi in zip(wsel, g[6:]):
+                    d_wb[i].add_(gi)
+                dh += g[1].double() * (s + TC[st])                     # through the stage time t = (s + TC) h
+                if st > 0:
+                    dh += TC[st] * dot(g_in, k[st - 1])                # through the stage input y + TC h k_{st-1}
+                gy_next.add_(g_in)
+                del g
+            gy = gy_next
+        dt_end = (dh / S).to(t_end.dtype).reshape(t_end.shape)
+        return (gy, glp, d_hyp[0], d_hyp[1], d_hyp[2], d_hyp[3], dt_end, None, None, None, None, None) + tuple(d_wb)
+
+
 def cnf_block_train(block, x, context, logpx, e):
     """x (BT,n,3), context (BT,zdim), logpx (BT,n,1), e (BT,n,3) fixed Hutchinson noise.  Forward direction
     t: 0 -> sqrt_end_time^2 with `block.rk4_steps` RK4 steps.  -> (x_T, logp_T), differentiable in every parameter."""
@@ -674,6 +768,15 @@ def cnf_block_train(block, x, context, logpx, e):
 
     t_end = block.sqrt_end_time * block.sqrt_end_time if block.train_T else torch.tensor(float(block.T), device=x.device)
     steps = block.rk4_steps
+    # BLOCK_NODE (config.train_cnf_block_node; off by default): the whole solve as one node with a tape of (BT,n,3) tensors only
+    # (CnfBlockSolve), where the fused-layer kernels and the bf16x6 CNF kernel apply; `_block_node_used` tells tests / tools which route ran
+    block._block_node_used = bool(BLOCK_NODE and fused and ops.CNF_BF16X6 and widths == (512, 512, 512, 3))
+    if block._block_node_used:
+        w1x, w2x = block._weights_x6()
+        wb = [p_ for l in layers for p_ in (l._layer.weight, l._layer.bias)]
+        y, lp = CnfBlockSolve.apply(x, logpx, G_lm, Bb_lm, tg_lm, tb_lm, t_end, e, w1x, w2x, steps, widths, *wb)
+        block.odefunc._num_evals.fill_(4 * steps)
+        return y, lp
     hstep = t_end / steps
     def rk4_step(t, y, lp):
         k1 = func(t, y, lp)

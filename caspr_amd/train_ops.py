@@ -166,6 +166,37 @@ def gn_rows_bwd(y, ns, C, gamma, beta, relu, mean, rstd, dgamma, dbeta, da=None,
     return out
 
 
+def cnf_train_fwd(y, logp, e, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_end, steps):
+    """Training forward of one CNF block in one launch (caspr_cnf_train_fwd_f32): y, e (BT,n,3), logp (BT,n,1), hyper (BT, >= 3078) and
+    tcol as ops.cnf_rk4 takes them, w1x / w2x = ops.pack_cnf_x6, t_end a one-element DEVICE tensor.
+    -> y_T (BT,n,3), logp_T (BT,n,1), stage inputs ys (steps,4,BT,n,3), stage outputs ka (steps,4,BT,n,3), knd (steps,4,BT,n,1)."""
+    _chk_f32(y, logp, e, hyper, tcol, w0, b0, b1, b2, w3, b3, t_end)
+    if y.dim() != 3 or y.shape[2] != 3:
+        raise ValueError("cnf_train_fwd: y must be (BT,n,3), got %s" % (tuple(y.shape),))
+    BT, n, _ = y.shape
+    if tuple(e.shape) != (BT, n, 3) or tuple(logp.shape) != (BT, n, 1):
+        raise ValueError("cnf_train_fwd: e %s / logp %s do not match y %s" % (tuple(e.shape), tuple(logp.shape), tuple(y.shape)))
+    if hyper.dim() != 2 or hyper.shape[0] != BT or hyper.stride(1) != 1 or hyper.shape[1] < 2 * (3 * 512 + 3) or tcol.numel() < 2 * (3 * 512 + 3):
+        raise ValueError("cnf_train_fwd: hyper must be (BT, >= 3078) rows and tcol hold 3078 floats, got %s / %s" % (tuple(hyper.shape), tuple(tcol.shape)))
+    if tuple(w0.shape) != (512, 3) or tuple(w3.shape) != (3, 512) or b0.numel() != 512 or b1.numel() != 512 or b2.numel() != 512 or b3.numel() != 3:
+        raise ValueError("cnf_train_fwd: the kernel is built for the 3-512-512-512-3 ODE function")
+    if w1x is None or w2x is None or w1x.numel() != _lib.load().caspr_cnf_x6_packed_bytes() or w2x.numel() != w1x.numel():
+        raise ValueError("cnf_train_fwd: the bf16x6 weight packs w1x / w2x (ops.pack_cnf_x6) are required")
+    if t_end.numel() != 1 or not t_end.is_cuda or steps <= 0:
+        raise ValueError("cnf_train_fwd: t_end must be a one-element device tensor and steps positive")
+    dev = y.device
+    out = torch.empty(BT, n, 3, device=dev, dtype=torch.float32)
+    lp_out = torch.empty(BT, n, 1, device=dev, dtype=torch.float32)
+    ys = torch.empty(steps, 4, BT, n, 3, device=dev, dtype=torch.float32)
+    ka = torch.empty(steps, 4, BT, n, 3, device=dev, dtype=torch.float32)
+    knd = torch.empty(steps, 4, BT, n, 1, device=dev, dtype=torch.float32)
+    with ops.timed("cnf_train_fwd"):
+        _lib.check(_lib.load().caspr_cnf_train_fwd_f32(_p(y), _p(hyper), hyper.stride(0), _p(tcol), _p(w0), _p(b0), _p(w1x), _p(b1), _p(w2x), _p(b2),
+                                                       _p(w3), _p(b3), 512, _p(t_end), int(steps), _p(e), _p(logp), _p(lp_out), _p(out), _p(ys), _p(ka),
+                                                       _p(knd), BT, n, _stream()), "caspr_cnf_train_fwd_f32")
+    return out, lp_out, ys, ka, knd
+
+
 class Segments:
     """CSR of a scatter: for every target row the contributing source rows (ascending) and their weights.
     Built from flat int tensors `target` (nnz), optional `weight` (nnz) and optional `src_rows` (nnz; default: entry e

@@ -191,6 +191,17 @@ int caspr_cnf_in_bwd_f32(const float *Y, const float *E, const float *W0, const 
                          const float *beta, const float *dH, long R, int n, int C, long blk, float *dgate,
                          float *dbeta, float *dW0_part, float *dY_part, void *stream);
 
+/* Training forward of one point-CNF block (csrc/ode_train_fwd.hip; train/flow_grad.py: CnfBlockSolve): `steps` classic RK4 steps over
+ * [0, *t_end] in the forward direction with the Hutchinson divergence for the given e, ONE launch, bf16x6 products with f32
+ * accumulation as caspr_cnf_rk4_x6_f32 (same hyper / tcol columns, same packs w1x / w2x of caspr_pack_weight_cnf_x6; H = 512).
+ * t_end: one float in DEVICE memory.  No MovingBatchNorm at either end.  Writes (y_out (BT,n,3), logp_out (BT,n)) and, for the
+ * reverse sweep, every evaluation's stage input ys (steps,4,BT,n,3) and stage outputs ka (steps,4,BT,n,3) = dy/dt,
+ * knd (steps,4,BT,n) = -e^T (df/dy) e.  No 512-wide tensor is written.  A frame's results do not depend on the batch around it.  */
+int caspr_cnf_train_fwd_f32(const float *y_in, const float *hyper, int ldh, const float *tcol, const float *w0, const float *b0,
+                            const void *w1x, const float *b1, const void *w2x, const float *b2, const float *w3, const float *b3,
+                            int H, const float *t_end, int steps, const float *e, const float *logp_in, float *logp_out,
+                            float *y_out, float *ys, float *ka, float *knd, int BT, int n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
