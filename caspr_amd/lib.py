@@ -97,6 +97,7 @@ SIGNATURES = {
     "caspr_pose_ransac_ws_bytes": (c_long, [c_int, c_int, c_int]),
     "caspr_pose_ransac_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_ulonglong, c_int,
                                       ctypes.c_void_p, c_ip, ctypes.c_void_p, c_ip, ctypes.c_void_p, c_long, c_stream]),
+    "caspr_base_sample_f32": (c_int, [c_int, c_int, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_void_p, c_float, c_fp, c_int, c_fp, c_fp, c_ip, c_stream]),
     # ---- include/caspr_hip_train.h (training tier) ----
     "caspr_gn_stats_train_f32": (c_int, [c_fp, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp, c_float, c_fp, c_fp, c_fp, c_fp, c_fp,
                                          ctypes.c_void_p, c_long, c_stream]),

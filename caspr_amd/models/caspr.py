@@ -3,7 +3,8 @@
 Drop-in for `caspr.models.caspr.CaSPR`: same constructor arguments, methods, return tuples and
 state_dict keys, so train.py / test.py / viz.py-style callers and reference
 checkpoints work unchanged.  Extra keyword-only knobs of this build: `cnf_rk4_steps`,
-`latent_rk4_steps` (fixed-step RK4 replaces torchdiffeq's adaptive dopri5).
+`latent_rk4_steps` (fixed-step RK4 replaces torchdiffeq's adaptive dopri5); `base_sampler` / `base_seed`
+(where decode's base samples are drawn: the host generators as the reference, or the counter-based device sampler).
 
 Inference: `encode`, `reconstruct`, `decode`, and `forward` for NLL / T-NOCS loss values.
 Training: in train() mode with grad enabled `forward` is differentiable end to end -- the encoder as one autograd node
@@ -84,6 +85,18 @@ def _drop_early_draw(owner):
 
 _GUARD_STREAM = {}
 _UNSET = object()
+_CONTOUR_RADII = {}   # (radii, device) -> float32 device tensor: the device sampler's sample_contours argument, copied to the device once
+
+
+def _contour_radii(radii, device):
+    if torch.is_tensor(radii):
+        return radii
+    key = (tuple(float(r) for r in radii), str(device))
+    if key not in _CONTOUR_RADII:
+        if len(_CONTOUR_RADII) >= 16:
+            _CONTOUR_RADII.clear()
+        _CONTOUR_RADII[key] = torch.tensor(key[0], dtype=torch.float32, device=device)
+    return _CONTOUR_RADII[key]
 
 
 def _guard_stream(device):
@@ -141,12 +154,24 @@ def _first_passing(diff_of, candidates, tol, refine=True, max_tries=3):
 
 
 class CaSPR(nn.Module):
+    # class-level defaults: a model pickled before these attributes existed keeps drawing on the host
+    base_sampler, base_seed, _base_draw = "host", 0, 0
+
     def __init__(self, radii_list=[0.02, 0.05, 0.1, 0.2, 0.4, 0.8], local_feat_size=512, latent_feat_size=1600,
                  ode_hidden_size=512, motion_feat_size=64, pretrain_tnocs=False, augment_quad=True, augment_pairs=True,
                  cnf_blocks=1, regress_tnocs=True, *, cnf_rk4_steps=8, latent_rk4_steps=2, check_tol=1e-5, latent_check_tol=None,
                  check_action="warn", check_points=64, cnf_method="rk4", cnf_atol=1e-5, cnf_rtol=1e-5,
-                 latent_method="rk4", latent_rtol=1e-3, latent_atol=1e-3):
+                 latent_method="rk4", latent_rtol=1e-3, latent_atol=1e-3, base_sampler="host", base_seed=0):
         super(CaSPR, self).__init__()
+        # Where decode() draws its base samples.  "host" (default): torch's CPU generator / numpy's global one, as the reference, so
+        # torch.manual_seed reproduces the reference's samples.  "device": the counter-based sampler (ops.base_samples): a sample is a
+        # function of (base_seed, draw number, global frame id, point, component), identical however a batch is sharded, and no host
+        # generator is touched.  The draw number is a plain int (deepcopy / torch.save keep it): one per drawing decode(), see seed_base().
+        if base_sampler not in ("host", "device"):
+            raise ValueError("base_sampler must be \"host\" or \"device\", got %r" % (base_sampler,))
+        self.base_sampler = base_sampler
+        self.base_seed = int(base_seed)
+        self._base_draw = 0
         # Run-time accuracy guard of the fixed-step integrators: ON by default at the reference's own tolerances, reporting as a
         # RuntimeWarning (check_action="raise": CasprAccuracyError; check_tol=None: off).  The reference's dopri5 controls its error at every
         # call (CNF atol = rtol = 1e-5, flow.py:96-99; latent ODE 1e-3, latent_ode_model.py:38,83); a fixed step count does not -- a trained
@@ -410,14 +435,47 @@ class CaSPR(nn.Module):
             ent["ev"].record(ent["stream"])
         return yd, ent["ev"], lp
 
-    def _base_samples(self, B, T, num_points, constant_in_time, truncate_std, sample_contours, y, like, early=None):
-        """The base-distribution draw of decode (caspr.py:228-256) -> (B*T, num_points, 3) on `like`'s device."""
+    def seed_base(self, seed, draw=0):
+        """Re-seed the device base sampler: the next drawing decode() / reconstruct() uses (seed, draw), the one after (seed, draw + 1), ...
+        (the host sampler follows torch.manual_seed / np.random.seed and ignores this).  A draw number lies in 0 .. 2^28 - 1 (the
+        counter's field for it); a decode() past the last one raises instead of reusing earlier samples: re-seed then."""
+        if not 0 <= int(draw) < (1 << 28):
+            raise ValueError("draw must lie in 0 .. 2^28 - 1, got %r" % (draw,))
+        self.base_seed, self._base_draw = int(seed), int(draw)
+
+    def _base_frame_ids(self, B, T, constant_in_time, frame_ids, device):
+        """Global frame ids of the device draw's rows, int64 on `device`: (B*T,) = sequence * T + t, or with constant_in_time (B,) =
+        sequence | 2^62 (one row per sequence; the high bit keeps it apart from every per-frame id).  Default: sequences 0 .. B-1."""
+        rows = B if constant_in_time else B * T
+        if frame_ids is None:
+            ids = torch.arange(rows, device=device, dtype=torch.int64)
+            return ids | (1 << 62) if constant_in_time else ids
+        ids = torch.as_tensor(frame_ids).to(device=device, dtype=torch.int64).reshape(-1).contiguous()
+        if ids.numel() != rows:
+            raise ValueError("frame_ids must hold %d ids (%s), got %d" % (rows, "one per sequence with constant_in_time" if constant_in_time else "B * T", ids.numel()))
+        return ids
+
+    def _base_samples(self, B, T, num_points, constant_in_time, truncate_std, sample_contours, y, like, early=None, frame_ids=None):
+        """The base-distribution draw of decode (caspr.py:228-256) -> (B*T, num_points, 3) on `like`'s device, and its log-density
+        (B*T, num_points) where the draw came with one (the device sampler), else None."""
         samp_batch = B if constant_in_time else B * T
         input_dim = self.cnf_args.input_dim
         samp_size = (samp_batch, num_points, input_dim)
+        logp_y = None
         if y is not None:
             y = y.to(like).reshape(B * T, num_points, input_dim)
             constant_in_time = False
+        elif self.base_sampler == "device":
+            # one launch on the current stream; contours take precedence over truncation, as in the reference's branch order
+            ids = self._base_frame_ids(B, T, constant_in_time, frame_ids, like.device)
+            if self._base_draw >= (1 << 28):
+                raise RuntimeError("the device base sampler has used all 2^28 draw numbers of this seed: call seed_base() with another seed")
+            radii = None if sample_contours is None else _contour_radii(sample_contours, like.device)
+            y, logp_y = ops.base_samples(samp_batch, num_points, self.base_seed, self._base_draw, ids,
+                                         trunc_std=truncate_std if sample_contours is None else None, radii=radii)
+            self._base_draw += 1
+            if constant_in_time:
+                logp_y = logp_y.view(B, 1, num_points).expand(B, T, num_points).reshape(B * T, num_points)
         elif sample_contours is not None:
             radii = sample_contours
             contours = []
@@ -439,15 +497,19 @@ class CaSPR(nn.Module):
             y = sample_gaussian(samp_size, truncate_std, device=like.device)
         if constant_in_time:
             y = y.view((B, 1, num_points, input_dim)).expand((B, T, num_points, input_dim)).reshape((B * T, num_points, input_dim))
-        return y.contiguous()
+        return y.contiguous(), logp_y
 
-    def decode(self, z, num_points=1024, constant_in_time=False, truncate_std=None, sample_contours=None, y=None, _early=None):
-        """caspr.py:204-267.  `y` (B,T,num_points,3) optionally supplies the base samples."""
+    def decode(self, z, num_points=1024, constant_in_time=False, truncate_std=None, sample_contours=None, y=None, _early=None, frame_ids=None):
+        """caspr.py:204-267.  `y` (B,T,num_points,3) optionally supplies the base samples.
+        frame_ids (device sampler only; ignored with the host sampler or a given `y`): the global ids the draw is keyed by, int64,
+        B*T of them (sequence * T + t) or, with constant_in_time, B (see _base_frame_ids); default: this batch is sequences 0 .. B-1."""
         B, T, H = z.size()
         input_dim = self.cnf_args.input_dim
         given = y is not None
-        y = self._base_samples(B, T, num_points, constant_in_time, truncate_std, sample_contours, y, z, early=_early)
-        if _early is not None and not given and sample_contours is None and truncate_std is None and not constant_in_time:
+        y, logp_y = self._base_samples(B, T, num_points, constant_in_time, truncate_std, sample_contours, y, z, early=_early, frame_ids=frame_ids)
+        if logp_y is not None:                       # the device draw's own launch wrote it (the same bits: csrc/base_sample.hip)
+            logp_y = logp_y.contiguous()
+        elif _early is not None and not given and sample_contours is None and truncate_std is None and not constant_in_time:
             logp_y = _early[2]                       # computed behind the draw's copy (same values: same op on the same tensor)
             logp_y.record_stream(torch.cuda.current_stream())
         else:
@@ -460,13 +522,17 @@ class CaSPR(nn.Module):
         return y.view((B, T, num_points, input_dim)), logp_y.view((B, T, num_points)), x.view((B, T, num_points, input_dim))
 
     def reconstruct(self, x, num_points=1024, constant_in_time=False, timestamps=None, max_timestamp=5.0,
-                    truncate_std=None, sample_contours=None, y=None, check_tol=_UNSET):
+                    truncate_std=None, sample_contours=None, y=None, check_tol=_UNSET, sequence_ids=None):
         """caspr.py:269-308 -> (y, logp_y, x, tnocs_pred).  `y` (B,T,num_points,3) optionally supplies the base samples.
-        check_tol: the accuracy guard's tolerance for THIS call (default: the model's `check_tol` attribute; None = off)."""
+        check_tol: the accuracy guard's tolerance for THIS call (default: the model's `check_tol` attribute; None = off).
+        sequence_ids (device sampler only; ignored with the host sampler or a given `y`): int64 (B,), the global index of each
+        sequence (default arange(B)); a shard that passes its sequences' global indices draws what the unsharded batch draws.
+        A tensor on x's device costs nothing; a list or host tensor is copied to the device synchronously at every call."""
         if check_tol is not _UNSET:
             prev, self.check_tol = self.check_tol, check_tol
             try:
-                return self.reconstruct(x, num_points, constant_in_time, timestamps, max_timestamp, truncate_std, sample_contours, y)
+                return self.reconstruct(x, num_points, constant_in_time, timestamps, max_timestamp, truncate_std, sample_contours, y,
+                                        sequence_ids=sequence_ids)
             finally:
                 self.check_tol = prev
         with torch.no_grad():
@@ -500,7 +566,18 @@ class CaSPR(nn.Module):
                 early_lat = _EarlyLatent(self.latent_ode, plan, st)
             z0, tnocs_pred = self.encoder(x, defer_tnocs=True, early=early_lat) if defer else self.encode(x)
             # the encoder is queued: draw the base samples on the host now (as the reference does inside decode), under it
-            early = self._draw_early(B, T, num_points, constant_in_time, x.device) if (defer and y is None and sample_contours is None) else None
+            early = None
+            if defer and y is None and sample_contours is None and self.base_sampler == "host":
+                early = self._draw_early(B, T, num_points, constant_in_time, x.device)
+            frame_ids = None
+            if self.base_sampler == "device" and y is None and sequence_ids is not None:
+                seq = torch.as_tensor(sequence_ids).to(device=x.device, dtype=torch.int64).reshape(-1)
+                if seq.numel() != B:
+                    raise ValueError("sequence_ids must hold B = %d ids, got %d" % (B, seq.numel()))
+                if constant_in_time:
+                    frame_ids = seq | (1 << 62)
+                else:
+                    frame_ids = (seq.view(B, 1) * T + torch.arange(T, device=x.device, dtype=torch.int64).view(1, T)).reshape(-1)
             with ops.timed("latent"):
                 z = self.aggregate_and_solve_latent(z0, all_times, plan, early_lat)
             self._early_latent_used = bool(early_lat is not None and early_lat.event is not None)     # for tests / tools
@@ -510,7 +587,7 @@ class CaSPR(nn.Module):
                 ops.BEFORE_CNF_LAUNCH = self.encoder.launch_tnocs        # queued between the flow's hyper conv and the flow (tpointnet2.py)
             try:
                 with ops.timed("decode"):
-                    y, logp_y, x = self.decode(z, num_points, constant_in_time, truncate_std, sample_contours, y=y, _early=early)
+                    y, logp_y, x = self.decode(z, num_points, constant_in_time, truncate_std, sample_contours, y=y, _early=early, frame_ids=frame_ids)
             finally:
                 ops.BEFORE_CNF_LAUNCH = None
                 if defer and JOIN_TNOCS_LATE:

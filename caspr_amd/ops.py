@@ -1136,3 +1136,50 @@ def ransac_rigid_from_correspondences(src, dst, threshold=0.015, num_hypotheses=
     _lib.check(L.caspr_pose_ransac_f32(_p(src), _p(dst), F, N, rs, K, n, float(threshold), int(seed) & 0xFFFFFFFFFFFFFFFF, int(bool(refine)),
                                        _p(T), _p(inliers), _p(rmse), _p(best), _p(ws), ws.numel(), _stream()), "caspr_pose_ransac_f32")
     return T, inliers.double() / N, rmse, inliers, best
+
+
+def base_samples(F, n, seed, draw, frame_ids, trunc_std=None, radii=None, raw=False):
+    """The decoder's base-distribution draw on the device (csrc/base_sample.hip; caspr.py:228-258): F frames of n points from a
+    counter-based generator (Philox4x32-10), each sample a function of (seed, draw, frame_ids[f], point, component) alone -- not of
+    the host generators, of F, or of which frames share a call.
+
+    frame_ids: (F,) int64 GPU tensor of global frame ids.  seed: any integer (taken mod 2^64); draw: 0 <= draw < 2^28.
+    trunc_std (> 0): models/utils.py:truncated_normal's rule; radii (R >= 1 values): the reference's sample_contours -- a float32
+    tensor on the device is used as it is, a sequence or host tensor costs a synchronous host-to-device copy per call; neither:
+    three normals per point.  raw=True also returns the (F,n,4) int32 Philox words of block 0.
+    -> y (F,n,3) f32, logp_y (F,n) f32 == standard_normal_logprob(y).sum(2) [, raw]."""
+    F, n, draw = int(F), int(n), int(draw)
+    if F < 1 or n < 1:
+        raise ValueError("F and n must be positive, got %d, %d" % (F, n))
+    if not 0 <= draw < (1 << 28):
+        raise ValueError("draw must lie in 0 .. 2^28 - 1, got %d" % draw)
+    if not torch.is_tensor(frame_ids) or not frame_ids.is_cuda:
+        raise ValueError("caspr_amd kernels need tensors on the GPU (frame_ids: %s): there is no CPU fallback"
+                         % (frame_ids.device if torch.is_tensor(frame_ids) else type(frame_ids).__name__))
+    _on_current_device(frame_ids)
+    if frame_ids.dtype != torch.int64 or frame_ids.dim() != 1 or frame_ids.shape[0] != F or not frame_ids.is_contiguous():
+        raise ValueError("frame_ids must be a contiguous int64 (F,) tensor with F = %d, got %s %s" % (F, frame_ids.dtype, tuple(frame_ids.shape)))
+    if trunc_std is not None and radii is not None:
+        raise ValueError("trunc_std and radii exclude each other")
+    ts = 0.0
+    if trunc_std is not None:
+        ts = float(trunc_std)
+        if not (ts > 0.0 and ts < float("inf")):
+            raise ValueError("trunc_std must be positive and finite, got %r" % (trunc_std,))
+    dev = frame_ids.device
+    rad, R = None, 0
+    if radii is not None:
+        if torch.is_tensor(radii) and radii.device == dev and radii.dtype == torch.float32:
+            rad = radii.reshape(-1).contiguous()
+        else:
+            rad = torch.as_tensor(radii, dtype=torch.float32).reshape(-1).to(dev).contiguous()
+        R = rad.numel()
+        if R < 1:
+            raise ValueError("radii must hold at least one radius")
+        _chk_f32(rad)
+    y = torch.empty(F, n, 3, device=dev, dtype=torch.float32)
+    logp = torch.empty(F, n, device=dev, dtype=torch.float32)
+    words = torch.empty(F, n, 4, device=dev, dtype=torch.int32) if raw else None
+    _lib.check(_lib.load().caspr_base_sample_f32(F, n, int(seed) & 0xFFFFFFFFFFFFFFFF, draw, _p(frame_ids), ts, _p(rad), R, _p(y), _p(logp),
+                                                 _p(words), _stream()), "caspr_base_sample_f32")
+    return (y, logp, words) if raw else (y, logp)

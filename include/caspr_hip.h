@@ -403,6 +403,19 @@ int caspr_pose_ransac_f32(const float *src, const float *dst, int F, int N, int 
                           double threshold, unsigned long long seed, int refine, double *T, int *inliers,
                           double *rmse, int *best, void *ws, long ws_bytes, void *stream);
 
+/* ---------------- base-distribution draw of the decoder on the device (caspr.py:228-258; models/utils.py:10-29;
+ * transform_utils.py:80-85) -- one launch writes y (F,n,3) and logp_y (F,n) = sum over components of -0.5 log(2 pi) - 0.5 y^2,
+ * rounded as standard_normal_logprob(y).sum(2) rounds it.  Counter-based: Philox4x32-10 keyed by `seed`, counter =
+ * (point, frame_ids[f] low word, high word, (draw << 4) | block), draw < 2^28; frame_ids (F) int64 is read on the device, so a
+ * sample depends on (seed, draw, frame id, point) only and a batch split over launches or ranks draws the same values.
+ * Uniforms u = ((word >> 8) + 0.5) 2^-24, normals by Box-Muller in f32.  Modes: radii != NULL (R >= 1 of them, f32, device):
+ * point i lies on contour min(i / (n / R), R - 1), a normalised uniform-cube draw scaled by its radius; else trunc_std > 0:
+ * each component is the first of four candidates inside (-trunc_std, trunc_std), candidate 0 if none is; else (trunc_std = 0,
+ * R = 0): three normals per point.  raw (optional, (F,n,4) int32): the four Philox words of block 0 of every point.
+ * Packing, candidate order and rounding: csrc/base_sample.hip.                                                               */
+int caspr_base_sample_f32(int F, int n, unsigned long long seed, unsigned int draw, const long long *frame_ids,
+                          float trunc_std, const float *radii, int R, float *y, float *logp, int *raw, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
