@@ -81,6 +81,15 @@ class CNF(nn.Module):
                                lambda: (ops.pack_cnf_x6(layers[1]._layer.weight.detach().contiguous()),
                                         ops.pack_cnf_x6(layers[2]._layer.weight.detach().contiguous())))
 
+    def _weights_h3(self):
+        """Two-plane f16 packs of the two hidden layers for the f16x3 sampling kernel (ops.CNF_SPLIT = "f16x3"; built on first use)."""
+        layers = self.odefunc.diffeq.layers
+        if layers[0]._layer.out_features != 512:
+            return None, None
+        return self._cache.get("wh3", [layers[1]._layer.weight, layers[2]._layer.weight],
+                               lambda: (ops.pack_cnf_h3(layers[1]._layer.weight.detach().contiguous()),
+                                        ops.pack_cnf_h3(layers[2]._layer.weight.detach().contiguous())))
+
     def end_time(self):
         """T_end = sqrt_end_time^2 (cnf.py:87-90), read back once per parameter version (a D2H sync otherwise
         sits between the encoder and every CNF launch)."""
@@ -124,9 +133,13 @@ class CNF(nn.Module):
                 self.last_nfe_per_frame = info["nfe"]
                 self.odefunc._num_evals += info["nfe"].max().to(self.odefunc._num_evals.dtype)
             return res
+        # the f16x3 split: plain sampling solves only (ops.cnf_rk4 routes).  The guard's check solve (_count_evals is False then) stays on
+        # bf16x6 at every check_points, also where it is too wide for the narrow kernel: it checks the step count, on the scheme it always used
+        w1h, w2h = self._weights_h3() if (ops.CNF_BF16X6 and ops.cnf_split() == "f16x3" and logpx is None and not self._narrow
+                                          and self._count_evals) else (None, None)
         res = ops.cnf_rk4(x.contiguous(), hyper, w["tcol"], w["w0"], w["b0"], w["w1p"], w["b1"], w["w2p"], w["b2"], w["w3"], w["b3"],
                           self.end_time(), self.rk4_steps, reverse, mbn_in, mbn_out, e=e,
-                          logp=None if logpx is None else logpx.contiguous(), w1x=w1x, w2x=w2x, narrow=self._narrow)
+                          logp=None if logpx is None else logpx.contiguous(), w1x=w1x, w2x=w2x, narrow=self._narrow, w1h=w1h, w2h=w2h)
         if self._count_evals:
             self.odefunc._num_evals += 4 * self.rk4_steps
         return res

@@ -255,6 +255,17 @@ _mode = _cfg.matmul            # caspr_amd/config.py (the environment only under
 CONV_BF16X6 = _mode == "bf16x6"      # pointwise convs (conv1x1) on the bf16x6 kernel where the shape allows
 CONV_X6W = _cfg.conv_x6w             # ... and the layers with >= 512 output channels on the 512-channel kernel
 CNF_BF16X6 = _mode == "bf16x6"       # point-CNF solves on the bf16x6 kernel
+CNF_SPLIT = _cfg.cnf_split           # "f16x3": the sampling solve (no divergence, n >= 128) on three f16 products per f32 product (csrc/ode_f16x3w.hip);
+                                     # matmul_mode()["cnf"] says "bf16x6" for both (the family; bench.py keys its roofline block on that string)
+
+
+def cnf_split():
+    """CNF_SPLIT, validated where it is read: the attribute is a run-time switch, and a misspelt value must not select bf16x6 silently."""
+    if CNF_SPLIT not in ("bf16x6", "f16x3"):
+        raise ValueError("caspr_amd.ops.CNF_SPLIT must be 'bf16x6' or 'f16x3', got %r" % (CNF_SPLIT,))
+    return CNF_SPLIT
+
+
 _X6_MIN_CIN = 192     # below this the f32 LDS kernel is used anyway (set-abstraction / input layers)
 # the 512-channel kernel (gemm_bf16x6w.hip) from this many input channels.  Round 3: 1024 (one workgroup per tile, prologue / epilogue
 # exposed: only the 1600-wide head layer's 50-chunk K loop amortised them).  Round 4: the kernel is persistent and its statistics
@@ -739,13 +750,15 @@ def _team_raise_if_failed(key, wait=False):
 
 def check_deferred_errors(wait=True):
     """Raise CasprHipError if an earlier asynchronous kernel reported a failure (the latent team kernel's barrier, the adaptive
-    latent solve's attempt budget), or
+    latent solve's attempt budget, the range guard of the f16x3 CNF solve), or
     CasprAccuracyError / warn if a run-time accuracy check of the fixed-step integrators came back above its tolerance
     (guard_track).  wait=True blocks until the status words of every outstanding solve / check have arrived."""
     for key in list(_team_status):
         _team_raise_if_failed(key, wait=wait)
     for key in list(_dp5_status):
         _dp5_raise_if_failed(key, wait=wait)
+    for key in list(_h3_status):
+        _h3_raise_if_failed(key, wait=wait)
     _guard_drain(wait=wait)
 
 
@@ -973,11 +986,64 @@ BEFORE_CNF_LAUNCH = None      # one-shot callable run between a CNF block's hype
                               # reconstruct() hands the encoder's deferred T-NOCS regression to it
 
 
+def pack_cnf_h3(w):
+    """(512,512) hidden-layer weight of the ODE function -> the two-plane f16 pack of caspr_cnf_rk4_h3_f32 (cnf_split = "f16x3"); the
+    layer's power-of-two scale is found on the device and stored behind the planes: no host synchronisation, capturable."""
+    _chk_f32(w)
+    if tuple(w.shape) != (512, 512):
+        raise ValueError("pack_cnf_h3: expected a (512,512) weight, got %s" % (tuple(w.shape),))
+    out = torch.empty(_lib.load().caspr_cnf_h3_packed_bytes(), device=w.device, dtype=torch.uint8)
+    _lib.check(_lib.load().caspr_pack_weight_cnf_h3(_p(w), w.stride(0), _p(out), _stream()), "caspr_pack_weight_cnf_h3")
+    return out
+
+
+# The f16x3 solve's range guard (csrc/ode_f16x3w.hip): a hidden activation that is not finite in f16 after the 2^4 scale poisons its
+# point with NaN and sets the launch's status word, which travels like the team kernel's: copied to pinned host memory behind the
+# launch, read when the copy has arrived (the next f16x3 solve on the stream, or check_deferred_errors).
+_h3_status = {}          # stream key -> [(pinned host tensor, event)], oldest first
+_h3_pool = []
+_h3_word = {}            # stream key -> the device word (zeroed by the C entry in front of every launch, copied out behind it)
+
+
+def _h3_raise_if_failed(key, wait=False):
+    ring = _h3_status.get(key)
+    failed = False
+    while ring:
+        host, ev = ring[0]
+        if wait:
+            ev.synchronize()
+        if not ev.query():
+            break
+        ring.pop(0)
+        failed = failed or int(host[0]) != 0
+        _h3_pool.append(host)
+    if failed:
+        raise _lib.CasprHipError("caspr_cnf_rk4_h3_f32: the range guard of the f16x3 point-CNF solve tripped: a hidden activation of the ODE "
+                                 "function reached 4095, which is not finite in f16 after the kernel's 2^4 prescale; the samples of the affected "
+                                 "points were set to NaN.  Remedy: cnf_split=\"bf16x6\" (caspr_amd.config.config.cnf_split / caspr_amd.ops.CNF_SPLIT), "
+                                 "the six-product bf16 kernel, which has f32's exponent range")
+
+
+def _h3_track(key, word):
+    ring = _h3_status.setdefault(key, [])
+    if len(ring) >= 64:                              # nobody drained for 64 solves: bound the backlog (blocks on the oldest)
+        ring[0][1].synchronize()
+        _h3_raise_if_failed(key)
+    host = _h3_pool.pop() if _h3_pool else torch.zeros(1, dtype=torch.int32).pin_memory()
+    ev = torch.cuda.Event()
+    host.copy_(word, non_blocking=True)
+    ev.record(torch.cuda.current_stream())
+    ring.append((host, ev))
+
+
 def cnf_rk4(y, hyper, tcol, w0, b0, w1p, b1, w2p, b2, w3, b3, t_end, steps, reverse, mbn_in=None, mbn_out=None,
-            e=None, logp=None, w1x=None, w2x=None, narrow=False):
+            e=None, logp=None, w1x=None, w2x=None, narrow=False, w1h=None, w2h=None):
     """Fixed-step RK4 of one CNF block (cnf.py:70-128).  y (BT,n,3); hyper (BT,ldh).  Returns x or (x, logp).
     w1x / w2x (pack_cnf_x6): when given, the bf16x6 kernel runs the solve (with or without the divergence).
-    narrow: the 64-point sampling kernel (a launch that does not fill the chip lasts as long as one workgroup: the accuracy guard)."""
+    narrow: the 64-point sampling kernel (a launch that does not fill the chip lasts as long as one workgroup: the accuracy guard).
+    w1h / w2h (pack_cnf_h3): when both are given and the call is a plain sampling solve (e is None, not narrow, n >= 128), the f16x3
+    kernel runs it (three f16 products per f32 product); every other call goes where it goes without them.  Its range guard reports
+    through check_deferred_errors (not tracked under stream capture, as latent_rk4)."""
     _chk_f32(y, hyper, tcol, w0, b0, b1, b2, w3, b3, mbn_in, mbn_out, e, logp)
     BT, n, _ = y.shape
     if y.dim() != 3 or y.shape[2] != 3:
@@ -993,6 +1059,25 @@ def cnf_rk4(y, hyper, tcol, w0, b0, w1p, b1, w2p, b2, w3, b3, t_end, steps, reve
             raise ValueError("cnf_rk4: %s must hold 12 floats [weight | bias | running_mean | running_var]" % name)
     out = torch.empty_like(y)
     lp_out = torch.empty(BT, n, 1, device=y.device, dtype=torch.float32) if e is not None else None
+    if w1h is not None and w2h is not None and e is None and not narrow and n >= 128:
+        nbytes = _lib.load().caspr_cnf_h3_packed_bytes()
+        if w1h.numel() != nbytes or w2h.numel() != nbytes or w1h.dtype != torch.uint8 or w2h.dtype != torch.uint8:
+            raise ValueError("cnf_rk4: w1h / w2h must be the packs of pack_cnf_h3")
+        key = (y.device.index, torch.cuda.current_stream().cuda_stream)
+        capturing = torch.cuda.is_current_stream_capturing()       # hipGraph capture: no event queries, no host copies
+        if not capturing:
+            _h3_raise_if_failed(key)                     # status of the previous solves on this stream, if it has arrived
+        word = _h3_word.get(key)
+        if word is None:
+            word = _h3_word[key] = torch.zeros(1, device=y.device, dtype=torch.int32)
+        with timed("cnf_rk4"):
+            _lib.check(_lib.load().caspr_cnf_rk4_h3_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1h), _p(b1), _p(w2h),
+                                                        _p(b2), _p(w3), _p(b3), w0.shape[0], float(t_end), int(steps), int(bool(reverse)),
+                                                        _p(mbn_in), _p(mbn_out), _p(word), _p(out), BT, n, _stream()),
+                       "caspr_cnf_rk4_h3_f32")
+        if not capturing:
+            _h3_track(key, word)
+        return out
     if w1x is not None and w2x is not None:
         with timed("cnf_rk4"):
             _lib.check(_lib.load().caspr_cnf_rk4_x6_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1x), _p(b1), _p(w2x),

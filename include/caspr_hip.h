@@ -355,6 +355,25 @@ int caspr_cnf_rk4_x6_f32(const float *y_in, const float *hyper, int ldh, const f
                          const float *e, const float *logp_in, float *logp_out, float *y_out, int BT,
                          int n, void *stream);
 
+/* The SAMPLING solve (no divergence) with the two hidden layers on THREE f16 products per f32 product instead of six bf16 ones
+ * (csrc/ode_f16x3w.hip; the Python host's config.cnf_split = "f16x3"): the geometry of the 128-point kernel above on
+ * v_mfma_f32_32x32x16_f16 with two round-to-nearest f16 planes per operand, a . b ~ a2 b1 + a1 b2 + a1 b1.  Exact power-of-two
+ * prescales keep the planes in f16's range: activations x 2^4, a layer's weights x 2^s with max |W| 2^s in [2^14, 2^15); s is
+ * computed on the device by caspr_pack_weight_cnf_h3 (no host synchronisation; capturable) and stored behind the pack.  Plane
+ * values below 2^-14 are flushed to zero explicitly.  tests/f16x3_ref.py restates the arithmetic.
+ *   w1h / w2h  the (512,512) hidden weights packed by caspr_pack_weight_cnf_h3 (caspr_cnf_h3_packed_bytes() bytes each);
+ *   status     one device word, zeroed by the entry on `stream` in front of the launch.  RANGE GUARD: a point one of whose
+ *              hidden activations is not finite in f16 after the 2^4 scale (|x| >= 4095) gets NaN in its three outputs and the
+ *              word is set to 1; every other point is unaffected.  The remedy is the bf16x6 entry above.
+ * Every other argument as caspr_cnf_rk4_x6_f32 without e / logp_in / logp_out; reverse takes no flag bits.               */
+long caspr_cnf_h3_packed_bytes(void);
+int caspr_pack_weight_cnf_h3(const float *w, int ldw, void *packed, void *stream);
+int caspr_cnf_rk4_h3_f32(const float *y_in, const float *hyper, int ldh, const float *tcol,
+                         const float *w0, const float *b0, const void *w1h, const float *b1,
+                         const void *w2h, const float *b2, const float *w3, const float *b3, int H,
+                         float t_end, int steps, int reverse, const float *mbn_in, const float *mbn_out,
+                         unsigned *status, float *y_out, int BT, int n, void *stream);
+
 /* ---------------- adaptive Dormand-Prince 5(4) solve of the same CNF block: models/cnf.py:96-118 (odeint with
  * method = dopri5, atol / rtol) -- what the reference runs on every call.  torchdiffeq 0.0.1's algorithm as oracle.model.dopri5_solve
  * restates it (initial step from d0 / d1 / d2, tol = atol + rtol max(|y0|, |y1|) per tensor of the state (x, logp), ratio =

@@ -4,6 +4,8 @@
 //   4: as 3, B operand non-negative   5: as 3, both non-negative   6: as 3, ONE exponent (values in [0.5, 1)), random signs
 //   7: the bf16x6 product sequence on three-plane operands as ROUNDING splits them (residual planes: random signs, 2^-8 / 2^-16 down),
 //      A = weights (random sign), B = activations (plane 0 positive)      8: the same as TRUNCATION splits them (planes keep the sign)
+//   9: the THREE-product sequence of a two-plane f16 split (v_mfma_f32_32x32x16_f16; plane 0 with a full 10-bit mantissa, the residual
+//      plane 2^-11 down with a random sign), A = weights, B = activations: 3 MFMAs per f32 product instead of 6
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
@@ -80,20 +82,63 @@ __global__ __launch_bounds__(256, 1) void k6(float *out, int iters, int trunc)
     for (int i = 0; i < 4; ++i) for (int j = 0; j < 16; ++j) s += c[i][j];
     out[blockIdx.x * 256 + threadIdx.x] = s;
 }
+// the three partial products of the f16 two-plane scheme, smallest first, alternating between two accumulators
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+__global__ __launch_bounds__(256, 1) void k3(float *out, int iters)
+{
+    f32x16 c[4] = {};
+    f16x8 a[2], b[2];
+    unsigned h = threadIdx.x * 2654435761u + blockIdx.x * 40503u + 12345u;
+    for (int j = 0; j < 8; ++j) {
+        h = h * 1664525u + 1013904223u;
+        const unsigned sa = (h >> 3) & 1, ea = 15 + ((h >> 5) & 7), eb = 15 + ((h >> 20) & 7);     // values in [1, 256): all planes normal
+        unsigned g = h;
+        for (int p = 0; p < 2; ++p) {
+            g = g * 1664525u + 1013904223u;
+            const unsigned drop = p ? ((g >> 28) & 3) : 0;                       // the residual starts 0..3 bits below the 11 of its parent
+            const unsigned sap = !p ? sa : (g >> 4) & 1, sbp = !p ? 0 : (g >> 6) & 1;
+            const unsigned short va = (unsigned short)((sap << 15) | ((ea - 11 * p - drop) << 10) | ((g >> 8) & 0x3ff));
+            const unsigned short vb = (unsigned short)((sbp << 15) | ((eb - 11 * p - drop) << 10) | ((g >> 18) & 0x3ff));
+            a[p][j] = __builtin_bit_cast(_Float16, va);
+            b[p][j] = __builtin_bit_cast(_Float16, vb);
+        }
+    }
+    for (int it = 0; it < iters; ++it) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int i0 = 2 * (u & 1), i1 = i0 + 1;
+            c[i0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1], b[0], c[i0], 0, 0, 0);
+            c[i1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1], b[0], c[i1], 0, 0, 0);
+            c[i0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[1], c[i0], 0, 0, 0);
+            c[i1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[1], c[i1], 0, 0, 0);
+            c[i0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[0], c[i0], 0, 0, 0);
+            c[i1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[0], c[i1], 0, 0, 0);
+        }
+        if ((it & 63) == 63)
+            for (int i = 0; i < 4; ++i) c[i] = c[i] * 0.5f;
+    }
+    float s = 0;
+    for (int i = 0; i < 4; ++i) for (int j = 0; j < 16; ++j) s += c[i][j];
+    out[blockIdx.x * 256 + threadIdx.x] = s;
+}
 int main()
 {
     float *out; (void)hipMalloc(&out, 256 * 256 * 4);
-    for (int data = 0; data < 9; ++data)
+    for (int data = 0; data < 10; ++data)
         for (int rep = 0; rep < 2; ++rep) {
             const int iters = data >= 7 ? 266667 : 400000;               // 24 MFMAs per iteration in the plane kernel, 16 in the other
             hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
             (void)hipEventRecord(e0);
-            if (data >= 7) k6<<<256, 256>>>(out, iters, data == 8);
+            if (data == 9) k3<<<256, 256>>>(out, iters);
+            else if (data >= 7) k6<<<256, 256>>>(out, iters, data == 8);
             else k<<<256, 256>>>(out, iters, data);
             (void)hipEventRecord(e1); (void)hipDeviceSynchronize();
             float ms; (void)hipEventElapsedTime(&ms, e0, e1);
-            printf("data %d: %8.2f ms  %7.1f TFLOP/s  (= %.3f GHz effective at 32 cycles / MFMA)\n", data, ms,
-                   256.0 * 4 * iters * (data >= 7 ? 24 : 16) * 32768.0 / (ms * 1e-3) / 1e12, 256.0 * 4 * iters * (data >= 7 ? 24 : 16) * 32.0 / (ms * 1e-3) / 1e9 / 1024.0);
+            const double tf = 256.0 * 4 * iters * (data >= 7 ? 24 : 16) * 32768.0 / (ms * 1e-3) / 1e12;
+            printf("data %d: %8.2f ms  %7.1f TFLOP/s  (= %.3f GHz effective at 32 cycles / MFMA)", data, ms, tf,
+                   256.0 * 4 * iters * (data >= 7 ? 24 : 16) * 32.0 / (ms * 1e-3) / 1e9 / 1024.0);
+            if (data >= 7) printf("  f32-equivalent %.1f TFLOP/s at %d MFMAs per product", tf / (data == 9 ? 3 : 6), data == 9 ? 3 : 6);
+            printf("\n");
         }
     return 0;
 }
