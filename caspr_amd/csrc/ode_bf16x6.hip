@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_x6_kernel(CnfX6Args a)
     const int tid = threadIdx.x, lane0 = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g0 = lane0 >> 4;
-    const int bt = blockIdx.y;
+    XC_FRAME_STEPS(a, bt, S, !DIV)
     // DIV: a wave's 16 columns are 8 points (j < 8) and their 8 tangent columns (j >= 8); the workgroup owns 32 points
     const int col = DIV ? blockIdx.x * (XC_COLS / 2) + 8 * wave + (lane0 & 7) : blockIdx.x * XC_COLS + 16 * wave + (lane0 & 15);
     const bool tg0 = DIV && (lane0 & 8);
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_x6_kernel(CnfX6Args a)
                                              (__attribute__((address_space(3))) void *)(wbuf + (p & 1) * XC_PIECE + (wave * 12 + s) * 1024), 16, 0, 0);
     };
     const double t0 = a.reverse ? (double)a.t_end : 0.0, t1 = a.reverse ? 0.0 : (double)a.t_end;
-    const double h = (t1 - t0) / (double)a.steps;
+    const double h = (t1 - t0) / (double)S;
     const float hh = (float)h, h2 = (float)(0.5 * h), h6 = (float)(h / 6.0);
 
     // the first piece of layer 1; every layer pass leaves the NEXT pass's first piece in flight
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_x6_kernel(CnfX6Args a)
     u32x4 bkw[2][3];              // B-fragment planes of the current / next k chunk, by chunk parity
     f32x4 tg_, tb, tw[3];         // table values of the half chunk being produced (gate, bias, input-layer weights)
 
-    for (int step = 0; step < a.steps; ++step) {
+    for (int step = 0; step < S; ++step) {
 #pragma unroll 1
         for (int stage = 0; stage < 4; ++stage) {
             const double tc = (stage == 0) ? 0.0 : (stage == 3 ? 1.0 : 0.5);
@@ -482,11 +482,12 @@ extern "C" int caspr_pack_weight_cnf_x6(const float *w, int ldw, void *packed, v
     return CASPR_OK;
 }
 
-extern "C" int caspr_cnf_rk4_x6_f32(const float *y_in, const float *hyper, int ldh, const float *tcol, const float *w0,
-                                    const float *b0, const void *w1x, const float *b1, const void *w2x, const float *b2,
-                                    const float *w3, const float *b3, int H, float t_end, int steps, int reverse,
-                                    const float *mbn_in, const float *mbn_out, const float *e, const float *logp_in,
-                                    float *logp_out, float *y_out, int BT, int n, void *stream)
+// steps_tab / max_steps / order: the per-frame table of caspr_cnf_rk4_x6_frames_f32 (sampling only), NULL / 0 / NULL from the plain entry
+static int cnf_rk4_x6_run(const float *y_in, const float *hyper, int ldh, const float *tcol, const float *w0,
+                          const float *b0, const void *w1x, const float *b1, const void *w2x, const float *b2,
+                          const float *w3, const float *b3, int H, float t_end, int steps, int reverse,
+                          const float *mbn_in, const float *mbn_out, const float *e, const float *logp_in,
+                          float *logp_out, float *y_out, int BT, int n, const int *steps_tab, int max_steps, const int *order, void *stream)
 {
     CASPR_REQUIRE(y_in && hyper && tcol && w0 && b0 && w1x && b1 && w2x && b2 && w3 && b3 && y_out, "cnf_rk4_x6: null pointer");
     CASPR_REQUIRE(H == XC_H, "cnf_rk4_x6: hidden width %d unsupported (kernel is built for 512-512-512, flow.py:89)", H);
@@ -504,6 +505,7 @@ extern "C" int caspr_cnf_rk4_x6_f32(const float *y_in, const float *hyper, int l
     const bool narrow = (reverse & CASPR_CNF_NARROW) != 0;      // the caller asks for the 64-point sampling kernel (include/caspr_hip.h)
     reverse &= 1;
     a.y_out = y_out; a.ldh = ldh; a.n = n; a.steps = steps; a.reverse = reverse; a.t_end = t_end;
+    a.steps_tab = steps_tab; a.max_steps = max_steps; a.order = order;
     // Kernel choice by the presence of e only, never by BT or n: a frame's result does not depend on the batch around it.
     // Sampling (no divergence): the 128-point kernel of ode_bf16x6w.hip; the debug build can force the 64-point one
     // (CASPR_X6_NARROW=1) for A/B timing (tools/cnf_x6w_trace.py).
@@ -526,4 +528,27 @@ extern "C" int caspr_cnf_rk4_x6_f32(const float *y_in, const float *hyper, int l
     else cnf_rk4_x6_kernel<false><<<dim3(ceil_div(n, XC_COLS), BT), dim3(256), XC_LDS, (hipStream_t)stream>>>(a);
     CASPR_CHECK_LAUNCH("cnf_rk4_x6");
     return CASPR_OK;
+}
+
+extern "C" int caspr_cnf_rk4_x6_f32(const float *y_in, const float *hyper, int ldh, const float *tcol, const float *w0,
+                                    const float *b0, const void *w1x, const float *b1, const void *w2x, const float *b2,
+                                    const float *w3, const float *b3, int H, float t_end, int steps, int reverse,
+                                    const float *mbn_in, const float *mbn_out, const float *e, const float *logp_in,
+                                    float *logp_out, float *y_out, int BT, int n, void *stream)
+{
+    return cnf_rk4_x6_run(y_in, hyper, ldh, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, H, t_end, steps, reverse, mbn_in, mbn_out, e, logp_in,
+                          logp_out, y_out, BT, n, nullptr, 0, nullptr, stream);
+}
+
+// the sampling solve with a step count per frame (cnf.py:70-128 with logpx = None; flow.py:96-99)
+extern "C" int caspr_cnf_rk4_x6_frames_f32(const float *y_in, const float *hyper, int ldh, const float *tcol, const float *w0,
+                                           const float *b0, const void *w1x, const float *b1, const void *w2x, const float *b2,
+                                           const float *w3, const float *b3, int H, float t_end, int reverse,
+                                           const float *mbn_in, const float *mbn_out, float *y_out, int BT, int n,
+                                           const int *steps_tab, int max_steps, const int *order, void *stream)
+{
+    CASPR_REQUIRE(steps_tab, "cnf_rk4_x6_frames: null step table");
+    CASPR_REQUIRE(max_steps >= 1 && max_steps <= 4096, "cnf_rk4_x6_frames: max_steps %d outside 1..4096", max_steps);
+    return cnf_rk4_x6_run(y_in, hyper, ldh, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, H, t_end, max_steps, reverse, mbn_in, mbn_out, nullptr,
+                          nullptr, nullptr, y_out, BT, n, steps_tab, max_steps, order, stream);
 }

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_x6w_kernel(CnfX6Args a)
 
     const int tid = threadIdx.x, lane0 = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int bt = blockIdx.y;
+    XC_FRAME_STEPS(a, bt, S, true)
     const float *hy = a.hyper + (long)bt * a.ldh;
     constexpr int BOFF = 3 * XC_H + 3;
 
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_x6w_kernel(CnfX6Args a)
         asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(dst), "v"(lane16), "s"(src) : "memory");
     };
     const double t0 = a.reverse ? (double)a.t_end : 0.0, t1 = a.reverse ? 0.0 : (double)a.t_end;
-    const double h = (t1 - t0) / (double)a.steps;
+    const double h = (t1 - t0) / (double)S;
     const float hh = (float)h, h2 = (float)(0.5 * h), h6 = (float)(h / 6.0);
 
     // pieces 0, 1, 2 and the first third of piece 3 in flight before the first one is consumed
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_x6w_kernel(CnfX6Args a)
             for (int pl = 0; pl < 3; ++pl) fX[u][pl] = *(const bf16x8 *)(A0 + (u * 3 + pl) * XW_FRAG);
     }
 
-    for (int step = 0; step < a.steps; ++step) {
+    for (int step = 0; step < S; ++step) {
 #pragma unroll 1
         for (int stage = 0; stage < 4; ++stage) {
             const double tc = (stage == 0) ? 0.0 : (stage == 3 ? 1.0 : 0.5);

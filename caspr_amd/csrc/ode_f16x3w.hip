@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
 
     const int tid = threadIdx.x, lane0 = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int bt = blockIdx.y;
+    XC_FRAME_STEPS(a, bt, S, true)
     const float *hy = a.hyper + (long)bt * a.ldh;
     constexpr int BOFF = 3 * XC_H + 3;
 
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
         asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(dst), "v"(lane16), "s"(src) : "memory");
     };
     const double t0 = a.reverse ? (double)a.t_end : 0.0, t1 = a.reverse ? 0.0 : (double)a.t_end;
-    const double h = (t1 - t0) / (double)a.steps;
+    const double h = (t1 - t0) / (double)S;
     const float hh = (float)h, h2 = (float)(0.5 * h), h6 = (float)(h / 6.0);
 
     // pieces 0..6 in flight before the first one is consumed
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
             for (int pl = 0; pl < 2; ++pl) fX[u][pl] = *(const f16x8 *)(A0 + (u * 2 + pl) * XH_FRAG);
     }
 
-    for (int step = 0; step < a.steps; ++step) {
+    for (int step = 0; step < S; ++step) {
 #pragma unroll 1
         for (int stage = 0; stage < 4; ++stage) {
             const double tc = (stage == 0) ? 0.0 : (stage == 3 ? 1.0 : 0.5);
@@ -626,10 +626,12 @@ extern "C" int caspr_pack_weight_cnf_h3(const float *w, int ldw, void *packed, v
     return CASPR_OK;
 }
 
-extern "C" int caspr_cnf_rk4_h3_f32(const float *y_in, const float *hyper, int ldh, const float *tcol, const float *w0,
-                                    const float *b0, const void *w1h, const float *b1, const void *w2h, const float *b2,
-                                    const float *w3, const float *b3, int H, float t_end, int steps, int reverse,
-                                    const float *mbn_in, const float *mbn_out, unsigned *status, float *y_out, int BT, int n, void *stream)
+// steps_tab / max_steps / order: the per-frame table of caspr_cnf_rk4_h3_frames_f32, NULL / 0 / NULL from the plain entry
+static int cnf_rk4_h3_run(const float *y_in, const float *hyper, int ldh, const float *tcol, const float *w0,
+                          const float *b0, const void *w1h, const float *b1, const void *w2h, const float *b2,
+                          const float *w3, const float *b3, int H, float t_end, int steps, int reverse,
+                          const float *mbn_in, const float *mbn_out, unsigned *status, float *y_out, int BT, int n,
+                          const int *steps_tab, int max_steps, const int *order, void *stream)
 {
     CASPR_REQUIRE(y_in && hyper && tcol && w0 && b0 && w1h && b1 && w2h && b2 && w3 && b3 && y_out && status, "cnf_rk4_h3: null pointer");
     CASPR_REQUIRE(H == XC_H, "cnf_rk4_h3: hidden width %d unsupported (kernel is built for 512-512-512, flow.py:89)", H);
@@ -642,6 +644,7 @@ extern "C" int caspr_cnf_rk4_h3_f32(const float *y_in, const float *hyper, int l
     a.e = nullptr; a.logp_in = nullptr; a.logp_out = nullptr; a.trace = nullptr; a.diag = 0;
     a.y_out = y_out; a.ldh = ldh; a.n = n; a.steps = steps; a.reverse = reverse & 1; a.t_end = t_end;
     a.status = status;
+    a.steps_tab = steps_tab; a.max_steps = max_steps; a.order = order;
     static CasprLdsOptIn optin;
     hipError_t err = caspr_lds_opt_in(optin, (const void *)cnf_rk4_h3w_kernel, XH_LDS);
     if (err != hipSuccess) {
@@ -656,4 +659,26 @@ extern "C" int caspr_cnf_rk4_h3_f32(const float *y_in, const float *hyper, int l
     cnf_rk4_h3w_kernel<<<dim3(ceil_div(n, XH_PTS), BT), dim3(256), XH_LDS, (hipStream_t)stream>>>(a);
     CASPR_CHECK_LAUNCH("cnf_rk4_h3");
     return CASPR_OK;
+}
+
+extern "C" int caspr_cnf_rk4_h3_f32(const float *y_in, const float *hyper, int ldh, const float *tcol, const float *w0,
+                                    const float *b0, const void *w1h, const float *b1, const void *w2h, const float *b2,
+                                    const float *w3, const float *b3, int H, float t_end, int steps, int reverse,
+                                    const float *mbn_in, const float *mbn_out, unsigned *status, float *y_out, int BT, int n, void *stream)
+{
+    return cnf_rk4_h3_run(y_in, hyper, ldh, tcol, w0, b0, w1h, b1, w2h, b2, w3, b3, H, t_end, steps, reverse, mbn_in, mbn_out, status, y_out,
+                          BT, n, nullptr, 0, nullptr, stream);
+}
+
+// the f16x3 sampling solve with a step count per frame (cnf.py:70-128 with logpx = None; flow.py:96-99)
+extern "C" int caspr_cnf_rk4_h3_frames_f32(const float *y_in, const float *hyper, int ldh, const float *tcol, const float *w0,
+                                           const float *b0, const void *w1h, const float *b1, const void *w2h, const float *b2,
+                                           const float *w3, const float *b3, int H, float t_end, int reverse,
+                                           const float *mbn_in, const float *mbn_out, unsigned *status, float *y_out, int BT, int n,
+                                           const int *steps_tab, int max_steps, const int *order, void *stream)
+{
+    CASPR_REQUIRE(steps_tab, "cnf_rk4_h3_frames: null step table");
+    CASPR_REQUIRE(max_steps >= 1 && max_steps <= 4096, "cnf_rk4_h3_frames: max_steps %d outside 1..4096", max_steps);
+    return cnf_rk4_h3_run(y_in, hyper, ldh, tcol, w0, b0, w1h, b1, w2h, b2, w3, b3, H, t_end, max_steps, reverse, mbn_in, mbn_out, status,
+                          y_out, BT, n, steps_tab, max_steps, order, stream);
 }

@@ -9,6 +9,16 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define XC_H 512
 
+// The frame and the RK4 step count of a sampling workgroup (see CnfX6Args::steps_tab / order).  Both are workgroup-uniform.  A row of
+// `order` outside 0 .. gridDim.y - 1 and a table entry outside 0 .. max_steps never reach an address or a loop bound as they are:
+// the first skips the workgroup, the second is clamped.
+// `on` = false (the divergence kernel): the plain frame and count, as a compile-time fact.
+#define XC_FRAME_STEPS(a, bt, S, on)                                                                     \
+    const int bt = ((on) && (a).order) ? (a).order[blockIdx.y] : (int)blockIdx.y;                        \
+    if ((on) && (unsigned)bt >= gridDim.y) return;                                                       \
+    const int S = ((on) && (a).steps_tab) ? min(max((a).steps_tab[bt], 0), (a).max_steps) : (a).steps;  \
+    if ((on) && S == 0) return;   /* before anything of the frame is read or written; no DMA is in flight yet */
+
 __device__ __forceinline__ void xc_split(float x, float &h1, float &h2, float &h3)
 {
     h1 = __uint_as_float(__float_as_uint(x) & 0xffff0000u);
@@ -43,6 +53,10 @@ struct CnfX6Args {
     float *y_out;
     int ldh, n, steps, reverse;
     float t_end;
+    // sampling kernels only (the *_frames_* entries; all NULL / 0 otherwise): a step count per frame and a launch order
+    const int *steps_tab;         // (BT) or NULL: frame bt takes min(max(steps_tab[bt], 0), max_steps) steps, 0 = the frame is skipped
+    int max_steps;
+    const int *order;             // (BT) or NULL: workgroup row blockIdx.y works on frame order[blockIdx.y]
     unsigned long long *trace;   // debug build: s_memtime stamps of workgroup (0,0), thread 0, RK4 step 0 / stage 1
     int diag;                    // debug build: timing experiments (CASPR_X6_DIAG)
 };

@@ -91,6 +91,13 @@ SIGNATURES = {
     "caspr_pack_weight_cnf_h3": (c_int, [c_fp, c_int, ctypes.c_void_p, c_stream]),
     "caspr_cnf_rk4_h3_f32": (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_fp, ctypes.c_void_p, c_fp, ctypes.c_void_p, c_fp, c_fp, c_fp, c_int, c_float,
                                      c_int, c_int, c_fp, c_fp, ctypes.c_void_p, c_fp, c_int, c_int, c_stream]),
+    "caspr_cnf_rk4_x6_frames_f32": (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_fp, ctypes.c_void_p, c_fp, ctypes.c_void_p, c_fp, c_fp, c_fp, c_int, c_float,
+                                            c_int, c_fp, c_fp, c_fp, c_int, c_int, c_ip, c_int, c_ip, c_stream]),
+    "caspr_cnf_rk4_h3_frames_f32": (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_fp, ctypes.c_void_p, c_fp, ctypes.c_void_p, c_fp, c_fp, c_fp, c_int, c_float,
+                                            c_int, c_fp, c_fp, ctypes.c_void_p, c_fp, c_int, c_int, c_ip, c_int, c_ip, c_stream]),
+    "caspr_cnf_steps_update_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_int, c_ip, c_ip, c_ip,
+                                           ctypes.c_void_p, c_stream]),
+    "caspr_cnf_steps_order": (c_int, [c_ip, c_int, c_ip, c_stream]),
     "caspr_cnf_dopri5_ws_bytes": (c_long, [c_int, c_int, c_int]),
     "caspr_cnf_dopri5_f32": (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_fp, ctypes.c_void_p, c_fp, ctypes.c_void_p, c_fp, c_fp, c_fp, c_int, c_float,
                                      c_float, c_float, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, ctypes.c_void_p, c_long,

@@ -156,13 +156,39 @@ def _first_passing(diff_of, candidates, tol, refine=True, max_tries=3):
 class CaSPR(nn.Module):
     # class-level defaults: a model pickled before these attributes existed keeps drawing on the host
     base_sampler, base_seed, _base_draw = "host", 0, 0
+    cnf_steps, cnf_steps_tol, cnf_steps_safety, cnf_steps_max, cnf_steps_points = "uniform", None, 1.2, 64, 64
 
     def __init__(self, radii_list=[0.02, 0.05, 0.1, 0.2, 0.4, 0.8], local_feat_size=512, latent_feat_size=1600,
                  ode_hidden_size=512, motion_feat_size=64, pretrain_tnocs=False, augment_quad=True, augment_pairs=True,
                  cnf_blocks=1, regress_tnocs=True, *, cnf_rk4_steps=8, latent_rk4_steps=2, check_tol=1e-5, latent_check_tol=None,
                  check_action="warn", check_points=64, cnf_method="rk4", cnf_atol=1e-5, cnf_rtol=1e-5,
-                 latent_method="rk4", latent_rtol=1e-3, latent_atol=1e-3, base_sampler="host", base_seed=0):
+                 latent_method="rk4", latent_rtol=1e-3, latent_atol=1e-3, base_sampler="host", base_seed=0,
+                 cnf_steps="uniform", cnf_steps_tol=None, cnf_steps_safety=1.2, cnf_steps_max=64, cnf_steps_points=64):
         super(CaSPR, self).__init__()
+        # How many RK4 steps the point CNF's SAMPLING solve (decode / reconstruct) takes.  "uniform" (default): cnf_rk4_steps for every
+        # frame.  "frame": a count per frame, chosen on the device at every call by a pilot on the first cnf_steps_points samples of
+        # each frame (ops.cnf_frame_steps: the ladder 1, 2, 4, .., cnf_steps_max, the guard's Richardson estimate against
+        # cnf_steps_tol x (1 + max |x|), refined below the passing rung by the fourth-order law x cnf_steps_safety).  cnf_steps_tol =
+        # None: check_tol, or 1e-5 without a guard.  Inference only; forward() (density, training) keeps cnf_rk4_steps.
+        if cnf_steps not in ("uniform", "frame"):
+            raise ValueError("cnf_steps must be \"uniform\" or \"frame\", got %r" % (cnf_steps,))
+        if cnf_steps == "frame":
+            if cnf_method != "rk4":
+                raise ValueError("cnf_steps=\"frame\" chooses RK4 step counts: it does not combine with cnf_method=%r" % (cnf_method,))
+            if not (isinstance(cnf_steps_max, int) and 2 <= cnf_steps_max <= 256 and cnf_steps_max & (cnf_steps_max - 1) == 0):
+                raise ValueError("cnf_steps_max must be a power of two in 2..256, got %r" % (cnf_steps_max,))
+            if not (1.0 <= float(cnf_steps_safety) < float("inf")):
+                raise ValueError("cnf_steps_safety must be finite and >= 1, got %r" % (cnf_steps_safety,))
+            if int(cnf_steps_points) < 1:
+                raise ValueError("cnf_steps_points must be positive, got %r" % (cnf_steps_points,))
+            if cnf_steps_tol is not None and not (0.0 < float(cnf_steps_tol) < float("inf")):
+                raise ValueError("cnf_steps_tol must be positive and finite, got %r" % (cnf_steps_tol,))
+        self.cnf_steps = cnf_steps
+        self.cnf_steps_tol = cnf_steps_tol
+        self.cnf_steps_safety = float(cnf_steps_safety)
+        self.cnf_steps_max = cnf_steps_max
+        self.cnf_steps_points = int(cnf_steps_points)
+        self.last_frame_steps = None        # frame mode: (steps, order, info) of the last decode(), device tensors (ops.cnf_frame_steps)
         # Where decode() draws its base samples.  "host" (default): torch's CPU generator / numpy's global one, as the reference, so
         # torch.manual_seed reproduces the reference's samples.  "device": the counter-based sampler (ops.base_samples): a sample is a
         # function of (base_seed, draw number, global frame id, point, component), identical however a batch is sharded, and no host
@@ -396,6 +422,90 @@ class CaSPR(nn.Module):
             if t_ is not None:
                 t_.record_stream(gs)
 
+    # ------------------------------------------------------------------------------------------ per-frame step counts
+    def _decode_frame_steps(self, y, z):
+        """decode()'s solve with cnf_steps="frame": the hyper conv of every block once, the pilot ladder on the first cnf_steps_points
+        samples of every frame through the whole flow (one table shared by all blocks, narrow kernel), then the solve with the chosen
+        (steps, order).  No host read anywhere: capturable.  y (BT,n,3), z (BT,H) -> x (BT,n,3)."""
+        from .cnf import CNF
+        if self._differentiable(y, z):
+            raise ValueError("cnf_steps=\"frame\" is an inference option: call decode() / reconstruct() under torch.no_grad() "
+                             "(no gradient through a solve with per-frame step counts)")
+        blocks = [l for l in self.point_cnf.chain if isinstance(l, CNF)]
+        if any(b.method != "rk4" for b in blocks):
+            raise ValueError("cnf_steps=\"frame\" chooses RK4 step counts: a dopri5 block has none")
+        BT, n = y.shape[0], y.shape[1]
+        g, s_max = min(self.cnf_steps_points, n), int(self.cnf_steps_max)
+        tol = self.cnf_steps_tol if self.cnf_steps_tol is not None else (self.check_tol if self.check_tol is not None else 1e-5)
+        yp = y[:, :g].contiguous()
+
+        def run_rung(tab):
+            for b in blocks:
+                b.frame_steps, b.frame_order, b.frame_max_steps = tab, None, s_max
+            return self.point_cnf(yp, z, reverse=True)
+        try:
+            for b in blocks:
+                b._hyper = b.hyper_of(z)
+            if ops.BEFORE_CNF_LAUNCH is not None:          # reconstruct()'s deferred T-NOCS regression: in front of the pilot, not of the solve
+                hook, ops.BEFORE_CNF_LAUNCH = ops.BEFORE_CNF_LAUNCH, None
+                hook()
+            for b in blocks:
+                b._count_evals, b.odefunc._count_evals, b._narrow = False, False, True
+            try:
+                with ops.timed("cnf_pilot"):
+                    steps, order, info = ops.cnf_frame_steps(run_rung, BT, g, tol, self.cnf_steps_safety, s_max, device=y.device)
+            finally:
+                for b in blocks:
+                    b._count_evals, b.odefunc._count_evals, b._narrow = True, True, False
+            for b in blocks:
+                b.frame_steps, b.frame_order, b.frame_max_steps = steps, order, s_max
+            with ops.timed("cnf_main"):
+                x = self.point_cnf(y, z, reverse=True)
+        finally:
+            for b in blocks:
+                b.frame_steps, b.frame_order, b.frame_max_steps, b._hyper = None, None, None, None
+        pilot_evals = 4 * info["pilot_steps"].max()
+        for b in blocks:
+            b.last_pilot_steps_per_frame = info["pilot_steps"]
+            b.odefunc._num_evals += pilot_evals.to(b.odefunc._num_evals.dtype)       # on the device, as the dopri5 route counts
+        self.last_frame_steps = (steps, order, info)
+        if self.check_tol is not None and not torch.cuda.is_current_stream_capturing():
+            self._guard_cnf_frames(blocks, y, z, x, steps, s_max)
+        return x
+
+    def _guard_cnf_frames(self, blocks, y, z, x, steps, s_max):
+        """The accuracy guard of a frame-mode solve: the first check_points samples of every frame once more with the table S_f // 2 on
+        the guard stream, behind the main launch; the criterion frame by frame -- diff_f / ((S_f / S'_f)^4 - 1) against check_tol x
+        (1 + max |x_f|) -- reduced on the device to the worst frame, which travels through the deferred channel (ops.guard_track)."""
+        g = min(int(self.check_points), y.shape[1])
+        gs = _guard_stream(y.device)
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream())
+        with torch.cuda.stream(gs), ops.untimed():
+            gs.wait_event(done)
+            half = torch.div(steps, 2, rounding_mode="floor").to(torch.int32)         # S_f >= 2: at least one step
+            try:
+                for b in blocks:
+                    b.frame_steps, b.frame_order, b.frame_max_steps = half, None, s_max
+                    b._count_evals, b.odefunc._count_evals, b._narrow = False, False, g <= 64
+                xh = self.point_cnf(y[:, :g].contiguous(), z, reverse=True)
+            finally:
+                for b in blocks:
+                    b.frame_steps, b.frame_order, b.frame_max_steps = None, None, None
+                    b._count_evals, b.odefunc._count_evals, b._narrow = True, True, False
+            xs = x[:, :g]
+            diff = (xs - xh).abs().flatten(1).amax(1).double()
+            scale = xs.abs().flatten(1).amax(1)
+            est = diff / ((steps.double() / half.double()) ** 4 - 1.0)
+            ratio = torch.nan_to_num(est / (float(self.check_tol) * (1.0 + scale.double())), nan=float("inf"))
+            worst = ratio.argmax()
+            ops.guard_track(est[worst].float(), scale[worst], {"name": "cnf", "tol": float(self.check_tol), "factor": 1.0, "steps": s_max, "other_steps": s_max // 2,
+                                                               "action": self.check_action,
+                                                               "what": "point CNF, per-frame step counts (at most the count named; the estimate is the worst "
+                                                                       "frame's, each against half its own count) (cnf.py:70-128; reference: dopri5 at atol = rtol = 1e-5)"})
+        for t_ in (y, z, x, steps):
+            t_.record_stream(gs)
+
     def gen_latent(self, z0, timestamps):
         """caspr.py:185-196."""
         return self.latent_ode(z0, timestamps)
@@ -515,10 +625,13 @@ class CaSPR(nn.Module):
         else:
             logp_y = standard_normal_logprob(y).view(B * T, num_points, -1).sum(2)
         z = z.reshape((B * T, H))
-        guard = self._guard_cnf_begin(y, z) if (self.check_tol is not None and y.is_cuda and not torch.is_grad_enabled()) else None
-        x = self.point_cnf(y, z, reverse=True)
-        if guard is not None:
-            self._guard_cnf_end(guard, x)
+        if self.cnf_steps == "frame" and y.is_cuda:
+            x = self._decode_frame_steps(y, z)
+        else:
+            guard = self._guard_cnf_begin(y, z) if (self.check_tol is not None and y.is_cuda and not torch.is_grad_enabled()) else None
+            x = self.point_cnf(y, z, reverse=True)
+            if guard is not None:
+                self._guard_cnf_end(guard, x)
         return y.view((B, T, num_points, input_dim)), logp_y.view((B, T, num_points)), x.view((B, T, num_points, input_dim))
 
     def reconstruct(self, x, num_points=1024, constant_in_time=False, timestamps=None, max_timestamp=5.0,

@@ -46,6 +46,15 @@ class CNF(nn.Module):
         self.last_nfe_per_frame = None   # dopri5: (BT,) int32 device tensor of the last counted solve
         self._count_evals = True      # False while the accuracy guard repeats a solve (CaSPR._guard_cnf): get_nfe() counts the real one only
         self._narrow = False          # True while the guard runs its check solve: the 64-point sampling kernel (ops.cnf_rk4(narrow=True))
+        # Per-frame step counts of the SAMPLING direction (CaSPR(cnf_steps="frame"); ops.cnf_frame_steps chooses them): when frame_steps
+        # -- a (BT,) int32 device tensor -- is set and no log-density is asked for, integrate() hands it (with frame_order, the launch
+        # order, and frame_max_steps, the kernels' clamp) to ops.cnf_rk4 in place of rk4_steps.  None: rk4_steps for every frame.
+        self.frame_steps = None
+        self.frame_order = None
+        self.frame_max_steps = None
+        self._hyper = None                       # frame mode: the hyper-network conv of the running decode(), computed once for pilot and solve
+        self.last_steps_per_frame = None         # frame mode: the table of the last counted solve, (BT,) int32 on the device
+        self.last_pilot_steps_per_frame = None   # ... and the RK4 steps its pilot spent per frame
         self._cache = WeightCache()
 
     def _weights(self):
@@ -98,6 +107,12 @@ class CNF(nn.Module):
             return self._cache.get("t_end", [p], lambda: float(p.detach() * p.detach()))
         return float(self.T)
 
+    def hyper_of(self, context):
+        """The gates / biases of the four hyper networks' context part for every frame: (BT, 2*(3H+3) padded)."""
+        w = self._weights()
+        # frames are the ROWS of this conv: row-invariant, so a frame's gates do not depend on the batch around it
+        return ops.conv1x1(w["hyp"], w["hyp_bias"], context.contiguous().view(1, context.shape[0], -1), row_invariant=True)[0]
+
     def integrate(self, x, context, logpx, reverse, mbn_in=None, mbn_out=None):
         """x (BT,n,3), context (BT,zdim), logpx (BT,n,1)|None.  MBN params fused at either end (kernel_params())."""
         if not x.is_cuda:
@@ -106,8 +121,7 @@ class CNF(nn.Module):
             raise ValueError("only the conditional CNF (flow.py:78-81) is supported")
         assert context is not None                                                              # cnf.py:78
         w = self._weights()
-        # frames are the ROWS of this conv: row-invariant, so a frame's gates do not depend on the batch around it
-        hyper = ops.conv1x1(w["hyp"], w["hyp_bias"], context.contiguous().view(1, context.shape[0], -1), row_invariant=True)[0]   # (BT, 2*(3H+3) padded)
+        hyper = self._hyper if self._hyper is not None else self.hyper_of(context)
         e = None
         if logpx is not None:
             e = self.odefunc._e
@@ -137,6 +151,16 @@ class CNF(nn.Module):
         # bf16x6 at every check_points, also where it is too wide for the narrow kernel: it checks the step count, on the scheme it always used
         w1h, w2h = self._weights_h3() if (ops.CNF_BF16X6 and ops.cnf_split() == "f16x3" and logpx is None and not self._narrow
                                           and self._count_evals) else (None, None)
+        if self.frame_steps is not None and logpx is None:
+            if torch.is_grad_enabled() and (x.requires_grad or context.requires_grad):
+                raise ValueError("CNF.frame_steps is an inference option: no gradient through a solve with per-frame step counts")
+            res = ops.cnf_rk4(x.contiguous(), hyper, w["tcol"], w["w0"], w["b0"], w["w1p"], w["b1"], w["w2p"], w["b2"], w["w3"], w["b3"],
+                              self.end_time(), self.frame_steps, reverse, mbn_in, mbn_out, w1x=w1x, w2x=w2x, narrow=self._narrow, w1h=w1h, w2h=w2h,
+                              order=self.frame_order, max_steps=self.frame_max_steps)
+            if self._count_evals:
+                self.last_steps_per_frame = self.frame_steps
+                self.odefunc._num_evals += 4 * self.frame_steps.max().to(self.odefunc._num_evals.dtype)      # on the device: no host read
+            return res
         res = ops.cnf_rk4(x.contiguous(), hyper, w["tcol"], w["w0"], w["b0"], w["w1p"], w["b1"], w["w2p"], w["b2"], w["w3"], w["b3"],
                           self.end_time(), self.rk4_steps, reverse, mbn_in, mbn_out, e=e,
                           logp=None if logpx is None else logpx.contiguous(), w1x=w1x, w2x=w2x, narrow=self._narrow, w1h=w1h, w2h=w2h)

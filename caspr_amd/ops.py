@@ -750,7 +750,7 @@ def _team_raise_if_failed(key, wait=False):
 
 def check_deferred_errors(wait=True):
     """Raise CasprHipError if an earlier asynchronous kernel reported a failure (the latent team kernel's barrier, the adaptive
-    latent solve's attempt budget, the range guard of the f16x3 CNF solve), or
+    latent solve's attempt budget, the range guard of the f16x3 CNF solve, a frame capped by the per-frame step controller), or
     CasprAccuracyError / warn if a run-time accuracy check of the fixed-step integrators came back above its tolerance
     (guard_track).  wait=True blocks until the status words of every outstanding solve / check have arrived."""
     for key in list(_team_status):
@@ -759,6 +759,8 @@ def check_deferred_errors(wait=True):
         _dp5_raise_if_failed(key, wait=wait)
     for key in list(_h3_status):
         _h3_raise_if_failed(key, wait=wait)
+    for key in list(_steps_status):
+        _steps_raise_if_capped(key, wait=wait)
     _guard_drain(wait=wait)
 
 
@@ -1036,16 +1038,51 @@ def _h3_track(key, word):
     ring.append((host, ev))
 
 
+CNF_MAX_TABLE_STEPS = 4096      # include/caspr_hip.h: the largest max_steps of the *_frames_* entries
+
+
+def _chk_frame_table(name, t, BT, device):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise ValueError("cnf_rk4: %s must be an int32 tensor on the GPU, got %s" % (name, t.device if torch.is_tensor(t) else type(t).__name__))
+    if t.device != device:
+        raise ValueError("cnf_rk4: %s lives on %s, the samples on %s" % (name, t.device, device))
+    if t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] != BT or not t.is_contiguous():
+        raise ValueError("cnf_rk4: %s must be a contiguous int32 (BT,) tensor with BT = %d, got %s %s" % (name, BT, t.dtype, tuple(t.shape)))
+
+
 def cnf_rk4(y, hyper, tcol, w0, b0, w1p, b1, w2p, b2, w3, b3, t_end, steps, reverse, mbn_in=None, mbn_out=None,
-            e=None, logp=None, w1x=None, w2x=None, narrow=False, w1h=None, w2h=None):
+            e=None, logp=None, w1x=None, w2x=None, narrow=False, w1h=None, w2h=None, order=None, max_steps=None, out=None):
     """Fixed-step RK4 of one CNF block (cnf.py:70-128).  y (BT,n,3); hyper (BT,ldh).  Returns x or (x, logp).
     w1x / w2x (pack_cnf_x6): when given, the bf16x6 kernel runs the solve (with or without the divergence).
     narrow: the 64-point sampling kernel (a launch that does not fill the chip lasts as long as one workgroup: the accuracy guard).
     w1h / w2h (pack_cnf_h3): when both are given and the call is a plain sampling solve (e is None, not narrow, n >= 128), the f16x3
     kernel runs it (three f16 products per f32 product); every other call goes where it goes without them.  Its range guard reports
-    through check_deferred_errors (not tracked under stream capture, as latent_rk4)."""
+    through check_deferred_errors (not tracked under stream capture, as latent_rk4).
+    steps may be a (BT,) int32 GPU tensor: a step count PER FRAME (plain sampling calls with the packs w1x / w2x only; routed as
+    above).  Frame f takes min(max(steps[f], 0), max_steps) steps (max_steps in 1..4096, default 4096); 0 skips the frame: its rows of
+    the result are left as allocated (uninitialised).  order: (BT,) int32 GPU tensor, the launch order of the frames (a permutation;
+    the result does not depend on it).  Frame f's rows equal, bit for bit, a call on that frame alone with its count.  out (with a
+    table only): a contiguous f32 tensor of y's shape to write into -- the rows of skipped frames keep what it holds."""
     _chk_f32(y, hyper, tcol, w0, b0, b1, b2, w3, b3, mbn_in, mbn_out, e, logp)
     BT, n, _ = y.shape
+    table = torch.is_tensor(steps)
+    if table:
+        if e is not None or logp is not None:
+            raise ValueError("cnf_rk4: a step table is for the sampling direction only (no e / logp)")
+        if w1x is None or w2x is None:
+            raise ValueError("cnf_rk4: a step table needs the bf16x6 weight packs w1x / w2x (pack_cnf_x6)")
+        _chk_frame_table("steps", steps, BT, y.device)
+        if order is not None:
+            _chk_frame_table("order", order, BT, y.device)
+        max_steps = CNF_MAX_TABLE_STEPS if max_steps is None else int(max_steps)
+        if not 1 <= max_steps <= CNF_MAX_TABLE_STEPS:
+            raise ValueError("cnf_rk4: max_steps must lie in 1..%d, got %d" % (CNF_MAX_TABLE_STEPS, max_steps))
+        if out is not None:
+            _chk_f32(out)
+            if tuple(out.shape) != tuple(y.shape) or out.device != y.device:
+                raise ValueError("cnf_rk4: out %s on %s does not match y %s on %s" % (tuple(out.shape), out.device, tuple(y.shape), y.device))
+    elif order is not None or max_steps is not None or out is not None:
+        raise ValueError("cnf_rk4: order / max_steps / out come with a step table (steps as a (BT,) int32 tensor)")
     if y.dim() != 3 or y.shape[2] != 3:
         raise ValueError("cnf_rk4: y must be (BT,n,3), got %s" % (tuple(y.shape),))
     if hyper.dim() != 2 or hyper.shape[0] != BT:
@@ -1057,7 +1094,7 @@ def cnf_rk4(y, hyper, tcol, w0, b0, w1p, b1, w2p, b2, w3, b3, t_end, steps, reve
     for name, m_ in (("mbn_in", mbn_in), ("mbn_out", mbn_out)):
         if m_ is not None and m_.numel() != 12:
             raise ValueError("cnf_rk4: %s must hold 12 floats [weight | bias | running_mean | running_var]" % name)
-    out = torch.empty_like(y)
+    out = torch.empty_like(y) if out is None else out
     lp_out = torch.empty(BT, n, 1, device=y.device, dtype=torch.float32) if e is not None else None
     if w1h is not None and w2h is not None and e is None and not narrow and n >= 128:
         nbytes = _lib.load().caspr_cnf_h3_packed_bytes()
@@ -1071,12 +1108,26 @@ def cnf_rk4(y, hyper, tcol, w0, b0, w1p, b1, w2p, b2, w3, b3, t_end, steps, reve
         if word is None:
             word = _h3_word[key] = torch.zeros(1, device=y.device, dtype=torch.int32)
         with timed("cnf_rk4"):
-            _lib.check(_lib.load().caspr_cnf_rk4_h3_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1h), _p(b1), _p(w2h),
-                                                        _p(b2), _p(w3), _p(b3), w0.shape[0], float(t_end), int(steps), int(bool(reverse)),
-                                                        _p(mbn_in), _p(mbn_out), _p(word), _p(out), BT, n, _stream()),
-                       "caspr_cnf_rk4_h3_f32")
+            if table:
+                _lib.check(_lib.load().caspr_cnf_rk4_h3_frames_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1h), _p(b1), _p(w2h),
+                                                                   _p(b2), _p(w3), _p(b3), w0.shape[0], float(t_end), int(bool(reverse)),
+                                                                   _p(mbn_in), _p(mbn_out), _p(word), _p(out), BT, n, _p(steps), max_steps, _p(order),
+                                                                   _stream()), "caspr_cnf_rk4_h3_frames_f32")
+            else:
+                _lib.check(_lib.load().caspr_cnf_rk4_h3_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1h), _p(b1), _p(w2h),
+                                                            _p(b2), _p(w3), _p(b3), w0.shape[0], float(t_end), int(steps), int(bool(reverse)),
+                                                            _p(mbn_in), _p(mbn_out), _p(word), _p(out), BT, n, _stream()),
+                           "caspr_cnf_rk4_h3_f32")
         if not capturing:
             _h3_track(key, word)
+        return out
+    if table:
+        with timed("cnf_rk4"):
+            _lib.check(_lib.load().caspr_cnf_rk4_x6_frames_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1x), _p(b1), _p(w2x),
+                                                               _p(b2), _p(w3), _p(b3), w0.shape[0], float(t_end),
+                                                               int(bool(reverse)) | (CNF_NARROW if narrow else 0), _p(mbn_in), _p(mbn_out),
+                                                               _p(out), BT, n, _p(steps), max_steps, _p(order), _stream()),
+                       "caspr_cnf_rk4_x6_frames_f32")
         return out
     if w1x is not None and w2x is not None:
         with timed("cnf_rk4"):
@@ -1092,6 +1143,111 @@ def cnf_rk4(y, hyper, tcol, w0, b0, w1p, b1, w2p, b2, w3, b3, t_end, steps, reve
                                                  _p(mbn_in), _p(mbn_out), _p(e), _p(logp), _p(lp_out), _p(out), BT, n, _stream()),
                    "caspr_cnf_rk4_f32")
     return out if e is None else (out, lp_out)
+
+
+# The per-frame step controller (csrc/cnf_frame_steps.hip): a frame that still fails the criterion at the largest rung is CAPPED there.
+# The count of capped frames travels like the f16x3 range guard's word: copied to pinned host memory behind the pilot, read when the
+# copy has arrived (the next pilot on the stream, or check_deferred_errors).
+_steps_status = {}       # stream key -> [(pinned host tensor, event, S_max, tol)], oldest first
+_steps_pool = []
+
+
+def _steps_raise_if_capped(key, wait=False):
+    ring = _steps_status.get(key)
+    msgs = []
+    while ring:
+        host, ev, s_max, tol = ring[0]
+        if wait:
+            ev.synchronize()
+        if not ev.query():
+            break
+        ring.pop(0)
+        if int(host[0]) != 0:
+            msgs.append("%d frame(s) capped at %d steps (tol %.1e)" % (int(host[0]), s_max, tol))
+        _steps_pool.append(host)
+    if msgs:
+        raise CasprAccuracyError("point CNF, per-frame step counts (cnf_steps=\"frame\"): " + "; ".join(msgs) + ": the step-halving estimate of "
+                                 "these frames still exceeds tol x (1 + max |x|) at the largest count the controller may choose, and they were "
+                                 "solved with it.  Raise cnf_steps_max (a power of two <= 256) or the tolerance")
+
+
+def _steps_track(key, capped, s_max, tol):
+    ring = _steps_status.setdefault(key, [])
+    if len(ring) >= 64:                              # nobody drained for 64 pilots: bound the backlog (blocks on the oldest)
+        ring[0][1].synchronize()
+        _steps_raise_if_capped(key)
+    host = _steps_pool.pop() if _steps_pool else torch.zeros(1, dtype=torch.int32).pin_memory()
+    ev = torch.cuda.Event()
+    host.copy_(capped.sum(dtype=torch.int32).reshape(1), non_blocking=True)
+    ev.record(torch.cuda.current_stream())
+    ring.append((host, ev, s_max, tol))
+
+
+def cnf_steps_update(x_prev, x_cur, P, tol, safety, max_steps, steps, next_tab, capped, stats):
+    """One update of the per-frame step controller after rung P (include/caspr_hip.h: caspr_cnf_steps_update_f32).  x_prev / x_cur
+    (BT,g,3) f32: the pilot solutions at P/2 and P steps; steps (in-out, 0 = undecided), next_tab, capped (BT,) int32; stats (BT,4) f64."""
+    _chk_f32(x_prev, x_cur)
+    if x_prev.dim() != 3 or x_prev.shape[2] != 3 or tuple(x_cur.shape) != tuple(x_prev.shape):
+        raise ValueError("cnf_steps_update: x_prev / x_cur must be (BT,g,3) of one shape, got %s / %s" % (tuple(x_prev.shape), tuple(x_cur.shape)))
+    BT, g, _ = x_prev.shape
+    for name, t in (("steps", steps), ("next_tab", next_tab), ("capped", capped)):
+        _chk_frame_table(name, t, BT, x_prev.device)
+    if stats.dtype != torch.float64 or tuple(stats.shape) != (BT, 4) or not stats.is_contiguous() or stats.device != x_prev.device:
+        raise ValueError("cnf_steps_update: stats must be a contiguous float64 (BT,4) tensor on the samples' device")
+    P, max_steps = int(P), int(max_steps)
+    if max_steps < 2 or max_steps > 256 or max_steps & (max_steps - 1):
+        raise ValueError("cnf_steps_update: max_steps must be a power of two in 2..256, got %d" % max_steps)
+    if P < 2 or P > max_steps or P & (P - 1):
+        raise ValueError("cnf_steps_update: the rung must be a power of two in 2..max_steps, got %d" % P)
+    if not (0.0 <= float(tol) < float("inf") and 1.0 <= float(safety) < float("inf")):
+        raise ValueError("cnf_steps_update: tol must be finite and >= 0, safety finite and >= 1, got %r / %r" % (tol, safety))
+    _lib.check(_lib.load().caspr_cnf_steps_update_f32(_p(x_prev), _p(x_cur), BT, g, P, float(tol), float(safety), max_steps, _p(steps), _p(next_tab),
+                                                      _p(capped), _p(stats), _stream()), "caspr_cnf_steps_update_f32")
+
+
+def cnf_steps_order(steps):
+    """(BT,) int32 step counts -> (BT,) int32: the stable permutation that sorts the frames by descending count (longest first)."""
+    if not torch.is_tensor(steps) or steps.dim() != 1:
+        raise ValueError("cnf_steps_order: steps must be a (BT,) int32 tensor on the GPU")
+    _chk_frame_table("steps", steps, steps.shape[0], steps.device)
+    if not 1 <= steps.shape[0] <= 65535:
+        raise ValueError("cnf_steps_order: 1..65535 frames, got %d" % steps.shape[0])
+    _on_current_device(steps)
+    order = torch.empty_like(steps)
+    _lib.check(_lib.load().caspr_cnf_steps_order(_p(steps), steps.shape[0], _p(order), _stream()), "caspr_cnf_steps_order")
+    return order
+
+
+def cnf_frame_steps(run_rung, BT, g, tol, safety=1.2, max_steps=64, device=None):
+    """Choose an RK4 step count per frame on the device (csrc/cnf_frame_steps.hip): the pilot ladder 1, 2, 4, .., max_steps.
+    run_rung(table) launches ONE rung -- the sampling solve of the g pilot points of every frame with the (BT,) int32 step table
+    `table` (0 = skip the frame) -- and returns its (BT,g,3) result.  After every rung from 2 on the update kernel decides the frames
+    whose Richardson estimate passes tol x (1 + max |x|) and doubles the others' table entry.  Every launch is enqueued
+    unconditionally (a rung whose table is all zero is an empty launch); nothing is read by the host, so the ladder is capturable.
+    -> (steps, order, info): steps (BT,) int32 in 2..max_steps, order (BT,) int32 = longest first, info = {"stats" (BT,4) f64
+    [d, bound, prediction, deciding rung], "capped" (BT,) int32, "pilot_steps" (BT,) int32 = the RK4 steps the pilot spent on the frame,
+    1 + 2 + .. + its deciding rung}.  A capped frame is reported through check_deferred_errors (not tracked under stream capture)."""
+    BT, g, max_steps = int(BT), int(g), int(max_steps)
+    if max_steps < 2 or max_steps > 256 or max_steps & (max_steps - 1):
+        raise ValueError("cnf_frame_steps: max_steps must be a power of two in 2..256, got %d" % max_steps)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    steps = torch.zeros(BT, device=dev, dtype=torch.int32)
+    capped = torch.zeros(BT, device=dev, dtype=torch.int32)
+    stats = torch.zeros(BT, 4, device=dev, dtype=torch.float64)
+    x_prev = run_rung(torch.ones(BT, device=dev, dtype=torch.int32))
+    tab, P = torch.full((BT,), 2, device=dev, dtype=torch.int32), 2
+    while P <= max_steps:
+        x_cur = run_rung(tab)
+        nxt = torch.empty_like(tab)
+        cnf_steps_update(x_prev, x_cur, P, tol, safety, max_steps, steps, nxt, capped, stats)
+        x_prev, tab, P = x_cur, nxt, 2 * P
+    order = cnf_steps_order(steps)
+    if not torch.cuda.is_current_stream_capturing():
+        key = (dev.index, torch.cuda.current_stream().cuda_stream)
+        _steps_raise_if_capped(key)
+        _steps_track(key, capped, max_steps, float(tol))
+    pilot = (2 * stats[:, 3] - 1).to(torch.int32)
+    return steps, order, {"stats": stats, "capped": capped, "pilot_steps": pilot}
 
 
 DP5_TRACE_HEAD, DP5_TRACE_ROW = 8, 5      # include/caspr_hip.h: the trace layout of caspr_cnf_dopri5_f32

@@ -374,6 +374,43 @@ int caspr_cnf_rk4_h3_f32(const float *y_in, const float *hyper, int ldh, const f
                          float t_end, int steps, int reverse, const float *mbn_in, const float *mbn_out,
                          unsigned *status, float *y_out, int BT, int n, void *stream);
 
+/* ---------------- the SAMPLING solve with an RK4 step count PER FRAME: cnf.py:70-128 with logpx = None / flow.py:96-99 (the reference's
+ * dopri5 chooses its steps at every call; a frame of this build's fixed-step solve may take its own count).  The kernels of
+ * caspr_cnf_rk4_x6_f32 (e == NULL: the 128-point one, or with reverse | CASPR_CNF_NARROW the 64-point one) and caspr_cnf_rk4_h3_f32;
+ * arguments as theirs without `steps` and without e / logp_in / logp_out, plus
+ *   steps_tab  (BT) int32, device: frame f takes min(max(steps_tab[f], 0), max_steps) steps; 0 SKIPS the frame -- its workgroups
+ *              return before they read or write anything of it, its rows of y_out keep their content;
+ *   max_steps  1..4096: the clamp of every table entry (a garbage table never becomes a long-running kernel);
+ *   order      (BT) int32, device, or NULL: workgroup row i works on frame order[i] (a permutation of 0..BT-1; a row outside that
+ *              range does nothing).  The result does not depend on it: longest-first shortens the tail of the launch.
+ * Frame f's rows are bit for bit what the plain entry writes for that frame alone at steps = its table entry.                */
+int caspr_cnf_rk4_x6_frames_f32(const float *y_in, const float *hyper, int ldh, const float *tcol,
+                                const float *w0, const float *b0, const void *w1x, const float *b1,
+                                const void *w2x, const float *b2, const float *w3, const float *b3, int H,
+                                float t_end, int reverse, const float *mbn_in, const float *mbn_out,
+                                float *y_out, int BT, int n, const int *steps_tab, int max_steps,
+                                const int *order, void *stream);
+int caspr_cnf_rk4_h3_frames_f32(const float *y_in, const float *hyper, int ldh, const float *tcol,
+                                const float *w0, const float *b0, const void *w1h, const float *b1,
+                                const void *w2h, const float *b2, const float *w3, const float *b3, int H,
+                                float t_end, int reverse, const float *mbn_in, const float *mbn_out,
+                                unsigned *status, float *y_out, int BT, int n, const int *steps_tab,
+                                int max_steps, const int *order, void *stream);
+
+/* The controller of those counts (csrc/cnf_frame_steps.hip; cnf.py:70-128 / flow.py:96-99: error control per call).  A pilot solves
+ * g points of every frame at 1, 2, 4, .., S_max steps (S_max a power of two in 2..256); after rung P >= 2, for every frame with
+ * steps[f] == 0 (undecided):  d = max |x_cur - x_prev| and bound = tol (1 + max |x_cur|) over the frame's (g,3) pilot rows (maxima in
+ * f32, the rest in f64), e = d / 15 the Richardson estimate of the P-step error.  e <= bound: steps[f] = 2 when P = 2, else
+ * clamp(ceil(P (e / bound)^(1/4) safety), P/2 + 1, P).  Otherwise, at P = S_max: steps[f] = S_max and capped[f] = 1; below it the
+ * frame stays undecided.  A non-finite value in either solution counts as a failure.  next_tab[f] = 2 P for a frame still
+ * undecided, else 0 (the next rung's table).  stats (BT,4) f64 = [d, bound, P (e / bound)^(1/4) safety, the rung that decided or 0]
+ * (NaN in the first three after a non-finite value); rows of decided frames are left alone, capped[] is written for examined frames.
+ * caspr_cnf_steps_order: order = the stable permutation that sorts frames by descending steps[] (ties: ascending frame).     */
+int caspr_cnf_steps_update_f32(const float *x_prev, const float *x_cur, int BT, int g, int P, double tol,
+                               double safety, int S_max, int *steps, int *next_tab, int *capped,
+                               double *stats, void *stream);
+int caspr_cnf_steps_order(const int *steps, int BT, int *order, void *stream);
+
 /* ---------------- adaptive Dormand-Prince 5(4) solve of the same CNF block: models/cnf.py:96-118 (odeint with
  * method = dopri5, atol / rtol) -- what the reference runs on every call.  torchdiffeq 0.0.1's algorithm as oracle.model.dopri5_solve
  * restates it (initial step from d0 / d1 / d2, tol = atol + rtol max(|y0|, |y1|) per tensor of the state (x, logp), ratio =
