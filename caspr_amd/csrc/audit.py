@@ -93,8 +93,10 @@ def audit_cnf_x6w(obj):
 
 def audit_cnf_h3w(obj):
     """cnf_rk4_h3w_kernel (ode_f16x3w.hip, the f16x3 copy of the kernel above): no scratch, exactly the accumulator moves the source
-    writes (256 zeroing writes + 256 in-place activation writes, 256 + 256 reads in pass 0 / passes 1-3), layer 1's MFMAs (8 pieces x 4
-    regions x 6) on a[..] in the f16 form, every other MFMA in the VGPR form, M0 written once per LDS-DMA instruction and by nothing else."""
+    writes (256 zeroing writes + 256 plane writes; 256 reads in pass 0, 256 plane reads in passes 1-3), layer 1's MFMAs (8 pieces x 4
+    regions x 6) on a[..] in the f16 form, every other MFMA in the VGPR form, M0 written once per LDS-DMA instruction and by nothing else.
+    Also returned, not judged here: cvt_pk, the number of v_cvt_pk_f16_f32 (one per value pair and plane the kernel splits;
+    tests/test_f16x3_planes_audit.py pins it)."""
     notes, dis = _code_object(obj)
     k = "_Z18cnf_rk4_h3w_kernel9CnfH3Args"
     meta, ins = _kernel(notes, dis, k)
@@ -110,7 +112,8 @@ def audit_cnf_h3w(obj):
     dma = count(r"global_load_lds_dwordx4")
     m0 = sum(1 for i in ins if re.search(r"\bm0\b", i))
     _need(dma > 20 and m0 == dma, "%s: %d LDS-DMA instructions, %d M0 accesses" % (k, dma, m0))
-    return {"kernel": k, "accvgpr_reads": r, "accvgpr_writes": w, "mfma": len(mfma), "mfma_on_acc": len(on_acc), "lds_dma": dma}
+    return {"kernel": k, "accvgpr_reads": r, "accvgpr_writes": w, "mfma": len(mfma), "mfma_on_acc": len(on_acc), "lds_dma": dma,
+            "cvt_pk": count(r"v_cvt_pk_f16_f32")}
 
 
 def audit_conv_x6w(obj):

@@ -13,6 +13,9 @@
 //    exact; they are undone in the stage's gate tables (g1 2^-s1 with the next layer's 2^4 folded in, g2 2^-(4 + s2)), at no cost;
 //  * the kernel carries the SCALED activation X = 16 softplus(x): the 2^4 sits in the tables of the producing layer, and
 //    softplus works on X directly (exp2 of |X| log2 e / 16, 16 ln 2 outside): the same roundings as on x, no extra instruction;
+//  * the accumulator file in layer 2 holds the two f16 PLANES of hidden layer 1's activations, not X: pass 0 splits a group of four
+//    values once and writes its four plane words over the four sums; passes 1-3 read them back as B operands and do no arithmetic
+//    (the bf16x6 kernel has to keep X: three bf16 planes are 48 bits a value);
 //  * plane values below 2^-14 (f16 subnormals) are flushed to zero explicitly, so nothing depends on the pipe's subnormal handling;
 //  * range guard: a lane tracks the maximum of the X it splits; a point whose maximum is not below 65520 (not finite in f16) gets NaN
 //    in all three outputs and the launch's status word is set (ops.check_deferred_errors reports it and names cnf_split="bf16x6");
@@ -85,6 +88,19 @@ __device__ __forceinline__ void xh_split2(XwPair &p, u32x4 (&bw)[2], int q)
     const float r0 = fabsf(p.r0) < XH_FLUSH ? 0.0f : p.r0, r1 = fabsf(p.r1) < XH_FLUSH ? 0.0f : p.r1;
     bw[0][q] = p.p1;
     bw[1][q] = xh_cvt_pk(r0, r1);
+}
+// a plane word (two f16) in / out of the accumulator file, bits untouched
+template <int N>
+__device__ __forceinline__ unsigned xh_acc_rd_u()
+{
+    unsigned x;
+    asm volatile("v_accvgpr_read_b32 %0, a%c1" : "=v"(x) : "i"(N));
+    return x;
+}
+template <int N>
+__device__ __forceinline__ void xh_acc_wr_u(unsigned x)
+{
+    asm volatile("v_accvgpr_write_b32 a%c1, %0" : : "v"(x), "i"(N) : XW_ACLOB);
 }
 
 __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
@@ -388,8 +404,9 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
                 tt[set][1] = ld4(s_hb1 + c);
             };
             // Producer of group GRP of k-step T_ (registers a[16 (T_ >> 1) + 8 (T_ & 1) + 4 GRP + r], r = 0..3), by slot.  FIRST
-            // pass: gate / bias / softplus applied in place (the scaled activation is what the accumulator file keeps); later
-            // passes: the stored activation is only split again.
+            // pass: gate / bias / softplus / split, and the group's four plane words (p1, p2 of pair a, p1, p2 of pair b: two f16
+            // planes of a value pair are exactly two 32-bit words) take the place of the four sums in the accumulator file; later
+            // passes: four reads straight into the B planes, no arithmetic (the range guard has seen every X in pass 0).
             auto l2_step = [&](auto I, auto TC, auto GC, auto FC, u32x4 (&bw)[2], int set) XW_INL {
                 constexpr int i = decltype(I)::value, t_ = decltype(TC)::value, grp = decltype(GC)::value;
                 constexpr bool first = decltype(FC)::value;
@@ -415,11 +432,7 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
                     }
                     if constexpr (i == 3) {
                         xh_sp3(pa, xmax);
-                        xw_acc_wr<base>(pa.x0);
-                        xw_acc_wr<base + 1>(pa.x1);
                         xh_sp3(pb, xmax);
-                        xw_acc_wr<base + 2>(pb.x0);
-                        xw_acc_wr<base + 3>(pb.x1);
                     }
                     if constexpr (i == 4) {
                         xh_split1(pa);
@@ -428,18 +441,18 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
                     if constexpr (i == 5) {
                         xh_split2(pa, bw, 2 * grp);
                         xh_split2(pb, bw, 2 * grp + 1);
+                        xh_acc_wr_u<base>(bw[0][2 * grp]);
+                        xh_acc_wr_u<base + 1>(bw[1][2 * grp]);
+                        xh_acc_wr_u<base + 2>(bw[0][2 * grp + 1]);
+                        xh_acc_wr_u<base + 3>(bw[1][2 * grp + 1]);
                     }
                 } else {
                     if constexpr (i == 0) {
-                        pa.x0 = xw_acc_rd<base>();
-                        pa.x1 = xw_acc_rd<base + 1>();
-                        pb.x0 = xw_acc_rd<base + 2>();
-                        pb.x1 = xw_acc_rd<base + 3>();
+                        bw[0][2 * grp] = xh_acc_rd_u<base>();
+                        bw[1][2 * grp] = xh_acc_rd_u<base + 1>();
+                        bw[0][2 * grp + 1] = xh_acc_rd_u<base + 2>();
+                        bw[1][2 * grp + 1] = xh_acc_rd_u<base + 3>();
                     }
-                    if constexpr (i == 1) xh_split1(pa);
-                    if constexpr (i == 2) xh_split2(pa, bw, 2 * grp);
-                    if constexpr (i == 3) xh_split1(pb);
-                    if constexpr (i == 4) xh_split2(pb, bw, 2 * grp + 1);
                 }
             };
             auto pass = [&](int q, auto FC) XW_INL {
@@ -456,6 +469,9 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
                 xw_for<0, 6>([&](auto I) XW_INL { l2_step(I, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, FC, b2w[0], 0); });
                 xw_for<0, 6>([&](auto I) XW_INL { l2_step(I, std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{}, FC, b2w[0], 1); });
                 if constexpr (first) l2_tab(0, 1, 0);
+                // passes 1-3: the plane words go from the accumulator read straight into hipcc's first MFMA, which does not see a
+                // VALU write in the asm statement and pads nothing: the two wait states by hand
+                else asm volatile("s_nop 1");
                 XW_FENCE;
                 xw_for<0, 16>([&](auto KC) XW_INL {
                     constexpr int kc = decltype(KC)::value;
