@@ -114,7 +114,9 @@ class PointNet2GroupingLayer(nn.Module):
 
 
 def three_nn(unknown, known):
-    """(B,n,3), (B,m,3) -> dist (B,n,3) [square roots], idx (B,n,3) int32 (pointnet2.py:514).  No gradient."""
+    """(B,n,3), (B,m,3) -> dist (B,n,3) [square roots], idx (B,n,3) int32 (pointnet2.py:514).  No gradient.
+    m <= 8192.  With m < 3 known points the slots m..2 keep what the upstream loop starts from: distance +inf and index 0 (the
+    weights of pointnet2.py:516-518 are then exactly 0 for them)."""
     return ops.three_nn(unknown.detach().contiguous(), known.detach().contiguous())
 
 

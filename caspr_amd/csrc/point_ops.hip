@@ -653,12 +653,23 @@ __global__ __launch_bounds__(256) void three_nn_kernel(const float *__restrict__
     }
 }
 
+// m <= 8192: 96 KiB of dynamic LDS at the limit; above m = 5461 (64 KiB) the kernel opts in like the ball queries.
+#define THREE_NN_MAX_M 8192
+static CasprLdsOptIn g_three_nn_optin;
+
 extern "C" int caspr_three_nn_f32(const float *unknown, const float *known, int B, int n, int m, float *dist,
                                   int32_t *idx, float *weight, void *stream)
 {
     CASPR_REQUIRE(unknown && known && dist && idx && B > 0 && n > 0 && m > 0, "three_nn: bad arguments");
-    CASPR_REQUIRE(m <= 8192, "three_nn: m=%d > 8192 unsupported", m);
-    three_nn_kernel<<<dim3(ceil_div(n, 256), B), dim3(256), (size_t)m * 12, (hipStream_t)stream>>>(
+    CASPR_REQUIRE(m <= THREE_NN_MAX_M, "three_nn: m=%d > %d unsupported (the known cloud is kept in LDS)", m, THREE_NN_MAX_M);
+    const size_t sh = (size_t)m * 3 * sizeof(float);
+    if (sh > 64 * 1024) {
+        if (caspr_lds_opt_in(g_three_nn_optin, (const void *)three_nn_kernel, THREE_NN_MAX_M * 3 * sizeof(float)) != hipSuccess) {
+            caspr_set_error("three_nn: hipFuncSetAttribute failed");
+            return CASPR_ELAUNCH;
+        }
+    }
+    three_nn_kernel<<<dim3(ceil_div(n, 256), B), dim3(256), sh, (hipStream_t)stream>>>(
         unknown, known, n, m, dist, idx, weight);
     CASPR_CHECK_LAUNCH("three_nn");
     return CASPR_OK;

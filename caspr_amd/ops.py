@@ -185,7 +185,9 @@ def group_points(xyz, new_xyz, feat, idx):
 
 
 def three_nn(unknown, known, with_weights=False):
-    """Kaolin `three_nn` (pointnet2.py:514): -> dist (B,n,3) [sqrt], idx (B,n,3) [, normalised inverse-distance weights :516-518]."""
+    """Kaolin `three_nn` (pointnet2.py:514): -> dist (B,n,3) [sqrt], idx (B,n,3) [, normalised inverse-distance weights :516-518].
+    At most 8192 known points (the cloud is kept in LDS; more raise).  With m < 3 known points the slots m..2 are never filled, as
+    upstream: distance +inf, index 0, and weight exactly 0 (1 / (inf + 1e-8)), so the weights of the m real neighbours still sum to 1."""
     _chk_f32(unknown, known)
     B, n, _ = unknown.shape
     m = known.shape[1]

@@ -378,3 +378,79 @@ def test_dataset_class_matches_reference(golden, tmp_path):
         DynamicPCLDataset(cfg, split="nope")
     with pytest.raises(FileNotFoundError):
         DynamicPCLDataset(cfg2, split="train")      # no train_split.txt in the split directory
+
+
+# ---------------------------------------------------------------------------------------------
+# the oracle's point operators at the edges tests/test_point_ops_edges.py holds the HIP kernels to
+# ---------------------------------------------------------------------------------------------
+def _three_nn_literal(unknown, known):
+    """The upstream three-slot loop restated LITERALLY (Pointnet2_PyTorch interpolate_gpu.cu, what Kaolin v0.1 adapts): best1..3
+    start at 1e40 (a double constant: +inf as a float), indices at 0, three strict `<` in a chain.  Coordinates are dyadic
+    rationals here, so every f32 operation is exact and fused / unfused arithmetic agree."""
+    dist, idx = [], []
+    for u in unknown:
+        b1 = b2 = b3 = float("inf")
+        i1 = i2 = i3 = 0
+        for k, q in enumerate(known):
+            d = float(np.float32(((u - q) ** 2).sum()))
+            if d < b1:
+                b3, i3, b2, i2, b1, i1 = b2, i2, b1, i1, d, k
+            elif d < b2:
+                b3, i3, b2, i2 = b2, i2, d, k
+            elif d < b3:
+                b3, i3 = d, k
+        dist.append([b1, b2, b3])
+        idx.append([i1, i2, i3])
+    return np.sqrt(np.array(dist, np.float32)), np.array(idx, np.int32)
+
+
+@pytest.mark.parametrize("m,dup", [(1, False), (2, False), (3, False), (2, True), (3, True), (12, True)])
+def test_three_nn_is_the_upstream_three_slot_loop(m, dup):
+    """Fewer than three known points (the unfilled slots keep +inf / index 0) and duplicate known points (the earlier index keeps
+    the earlier slot) on a coarse grid where most distances tie."""
+    rng = np.random.default_rng(10 * m + dup)
+    known = (rng.integers(0, 4, (m, 3)) / 4.0 + np.array([1.0, 0.5, 2.0])).astype(np.float32)
+    if dup:
+        known[m // 2:] = known[:m - m // 2]
+    unknown = (rng.integers(0, 8, (40, 3)) / 8.0 + np.array([1.0, 0.5, 2.0])).astype(np.float32)
+    unknown[:m] = known                                                  # distance 0, twice where the point is duplicated
+    wd, wi = _three_nn_literal(unknown, known)
+    d, i = P.three_nn(torch.from_numpy(unknown).unsqueeze(0), torch.from_numpy(known).unsqueeze(0))
+    assert np.array_equal(i[0].numpy(), wi) and np.array_equal(d[0].numpy(), wd)
+    for s in range(min(m, 3), 3):
+        assert np.isposinf(d[0, :, s].numpy()).all() and (i[0, :, s].numpy() == 0).all()
+    # the weights the reference builds from them (pointnet2.py:516-518): finite, and exactly 0 for an unfilled slot
+    inv = 1.0 / (d + 1e-8)
+    w = inv / inv.sum(dim=2, keepdim=True)
+    assert bool(torch.isfinite(w).all()) and all(bool((w[0, :, s] == 0).all()) for s in range(min(m, 3), 3))
+
+
+def test_three_nn_largest_cloud_against_f64_topk():
+    """m = 8192 (the largest known cloud the HIP entry takes): indices against an f64 top-3, on unknown points whose four nearest
+    f64 squared distances are more than 1e-6 apart -- 100x the f32 rounding of a squared distance of this size (|d2| < 0.1,
+    coordinates of magnitude ~1: 5 roundings of 6e-8 * 0.3 each), so no near-tie decides a case."""
+    B, m = 2, 8192
+    known = rnd(41, B, m, 3)
+    cand = rnd(42, B, 400, 3, scale=0.7)
+    d2 = ((cand.double().unsqueeze(2) - known.double().unsqueeze(1)) ** 2).sum(-1)            # (B,400,m)
+    top, ti = torch.topk(d2, 4, dim=2, largest=False)
+    clear = ((top[:, :, 1:] - top[:, :, :-1]).min(dim=2)[0] > 1e-6).all(dim=0)
+    assert int(clear.sum()) >= 200, int(clear.sum())
+    unknown = cand[:, clear].contiguous()
+    d, i = P.three_nn(unknown, known)
+    assert torch.equal(i.long(), ti[:, clear, :3])
+    close(d, top[:, clear, :3].sqrt().numpy(), 1e-6)
+
+
+@pytest.mark.parametrize("n,m", [(1, 1), (1024, 1025)])
+def test_chamfer_against_f64_brute_force(n, m):
+    """Squared nearest-neighbour distances both ways.  A squared distance in f32: three subtractions (1 rounding each, squared: 2 u),
+    one product and two fused multiply-adds (at most 3 more on a term) -> relative error <= 5 u to first order, 6 u with the
+    second-order terms; the minimum over perturbed values moves by no more than the largest perturbation of the smaller one."""
+    p, q = rnd(43 + n, 2, n, 3, scale=0.5), rnd(44 + m, 2, m, 3, scale=0.5)
+    d2 = ((p.double().unsqueeze(2) - q.double().unsqueeze(1)) ** 2).sum(-1)
+    w1, w2 = d2.min(dim=2)[0], d2.min(dim=1)[0]
+    d1, d2_ = P.chamfer(p, q)
+    assert tuple(d1.shape) == (2, n) and tuple(d2_.shape) == (2, m)
+    for got, want in ((d1, w1), (d2_, w2)):
+        assert bool(((got.double() - want).abs() <= 6 * 2.0 ** -24 * want).all()), float(((got.double() - want).abs() / want).max())
