@@ -1,4 +1,4 @@
-"""Code-object audit of the kernels that manage the accumulator file by hand (ode_bf16x6w.hip, its f16x3 copy ode_f16x3w.hip, gemm_bf16x6w.hip).
+"""Code-object audit of the kernels that manage the accumulator file by hand (ode_bf16x6w.hip, its f16x3 copy ode_f16x3w.hip, gemm_bf16x6w.hip, its f16x3 copy gemm_f16x3w.hip).
 
 Both keep 256 live values at FIXED addresses a0..a255 across separate inline-asm statements.  A clobber list does not reserve
 registers between statements: what keeps hipcc out of the AGPRs is the hidden flag -amdgpu-mfma-vgpr-form (build.py EXTRA) plus the
@@ -136,7 +136,28 @@ def audit_conv_x6w(obj):
     return out
 
 
-AUDITS = {"ode_bf16x6w.hip": audit_cnf_x6w, "ode_f16x3w.hip": audit_cnf_h3w, "gemm_bf16x6w.hip": audit_conv_x6w}
+def audit_conv_h3w(obj):
+    """conv1x1_h3w_kernel (gemm_f16x3w.hip, the f16x3 copy of the kernel above; all instantiations): no scratch, the accumulator file
+    zeroed once in the prologue and read out + zeroed again in the two instances of the tile read-out (3 x 256 writes, 2 x 256 reads), two
+    chunk bodies of 96 MFMAs, every one v_mfma_f32_32x32x16_f16 on a[..].  Also returned, not judged: cvt_pk, the number of
+    v_cvt_pk_f16_f32 (one per value pair and plane the kernel splits)."""
+    notes, dis = _code_object(obj)
+    kernels = re.findall(r"<(_Z18conv1x1_h3w_kernelI[^>]*)>:", dis)
+    _need(len(kernels) >= 4, "conv1x1_h3w_kernel: %d instantiations found" % len(kernels))
+    out = []
+    for k in kernels:
+        meta, ins = _kernel(notes, dis, k)
+        count = lambda pat: sum(1 for i in ins if re.match(pat, i))
+        _no_spills(meta, ins, k)
+        r, w = count(r"v_accvgpr_read_b32"), count(r"v_accvgpr_write_b32")
+        _need(w == 768 and r == 512 and count(r"v_accvgpr_mov") == 0, "%s: %d reads / %d writes of the accumulator file (512 / 768 in the source)" % (k, r, w))
+        mfma = [i for i in ins if i.startswith("v_mfma")]
+        _need(len(mfma) == 2 * 96 and all(re.match(r"v_mfma_f32_32x32x16_f16 a\[", i) for i in mfma), "%s: %d MFMAs, not all v_mfma_f32_32x32x16_f16 on a[..]" % (k, len(mfma)))
+        out.append({"kernel": k, "accvgpr_reads": r, "accvgpr_writes": w, "mfma": len(mfma), "cvt_pk": count(r"v_cvt_pk_f16_f32")})
+    return out
+
+
+AUDITS = {"ode_bf16x6w.hip": audit_cnf_x6w, "ode_f16x3w.hip": audit_cnf_h3w, "gemm_bf16x6w.hip": audit_conv_x6w, "gemm_f16x3w.hip": audit_conv_h3w}
 
 
 def audit_objects(objs_by_source):

@@ -6,7 +6,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.abspath(os.path.join(HERE, "..", "..")))
-SOURCES = ["point_ops.hip", "gemm.hip", "gemm_bf16x6.hip", "gemm_bf16x6w.hip", "sa_mlp.hip", "ode.hip", "ode_bf16x6.hip", "ode_bf16x6w.hip", "ode_f16x3w.hip", "cnf_frame_steps.hip", "ode_dp5.hip", "ode_train_fwd.hip", "ode_latent_dp5.hip", "backward.hip", "backward_points.hip", "backward_flow.hip", "emd.hip", "pose.hip", "base_sample.hip"]
+SOURCES = ["point_ops.hip", "gemm.hip", "gemm_bf16x6.hip", "gemm_bf16x6w.hip", "gemm_f16x3w.hip", "sa_mlp.hip", "ode.hip", "ode_bf16x6.hip", "ode_bf16x6w.hip", "ode_f16x3w.hip", "cnf_frame_steps.hip", "ode_dp5.hip", "ode_train_fwd.hip", "ode_latent_dp5.hip", "backward.hip", "backward_points.hip", "backward_flow.hip", "emd.hip", "pose.hip", "base_sample.hip"]
 EXTRA = {"point_ops.hip": ["-ffp-contract=off"], "emd.hip": ["-ffp-contract=off"], "pose.hip": ["-ffp-contract=off"],
          "cnf_frame_steps.hip": ["-ffp-contract=off"],   # its f64 decisions are restated operation by operation (tests/frame_steps_ref.py)
          "base_sample.hip": ["-ffp-contract=off"],   # its log-density must round as ATen's separate kernels do (see the file's header)
@@ -18,7 +18,8 @@ EXTRA = {"point_ops.hip": ["-ffp-contract=off"], "emd.hip": ["-ffp-contract=off"
          # must take the VGPR form there, or it would park them in AGPRs it believes free (see the kernel's header)
          "ode_bf16x6w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
          "ode_f16x3w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],   # the same, on f16
-         "gemm_bf16x6w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"]}
+         "gemm_bf16x6w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
+         "gemm_f16x3w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"]}   # its f16x3 copy
 # CASPR_BUILD_DEBUG=1: the flavour with phase-trace hooks and experiment switches (-DCASPR_DEBUG_HOOKS, see common.h), built
 # next to the production library as libcaspr_hip_debug.so with its own objects; tools/*_phase_trace.py load it.
 DEBUG = os.environ.get("CASPR_BUILD_DEBUG", "0") not in ("0", "")
@@ -47,11 +48,11 @@ def _stale(target, deps):
 def build(force=False, verbose=False):
     inc = os.path.join(HERE, "..", "..", "include")
     # (this file is a dependency of every object: the flag set lives here)
-    hdrs = [os.path.abspath(__file__)] + [os.path.join(HERE, h) for h in ("common.h", "ode_x6.h", "ode_x6w_agprs.h", "x6w_common.h")] + sorted(os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h"))
+    hdrs = [os.path.abspath(__file__)] + [os.path.join(HERE, h) for h in ("common.h", "ode_x6.h", "ode_x6w_agprs.h", "x6w_common.h", "f16x3_common.h")] + sorted(os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h"))
     objs, jobs, by_src = [], [], {}
     for s in SOURCES:
         src = os.path.join(HERE, s)
-        xw = XW_EXP if (XW_EXP and s in ("ode_bf16x6w.hip", "gemm_bf16x6w.hip")) else ""
+        xw = XW_EXP if (XW_EXP and s in ("ode_bf16x6w.hip", "gemm_bf16x6w.hip", "gemm_f16x3w.hip")) else ""
         obj = os.path.join(HERE, s.replace(".hip", (".dbg_xw%s.o" % xw) if xw else (".dbg.o" if DEBUG else ".o")))
         objs.append(obj)
         if not xw:
@@ -84,7 +85,7 @@ def build(force=False, verbose=False):
                     raise
                 import warnings
                 warnings.warn("caspr_amd build: code-object audit FAILED and was skipped on request (CASPR_SKIP_AUDIT=1):\n%s\n"
-                              "run `pytest -m gpu` before trusting cnf_rk4_x6w_kernel / cnf_rk4_h3w_kernel / conv1x1_x6w_kernel" % e, RuntimeWarning)
+                              "run `pytest -m gpu` before trusting cnf_rk4_x6w_kernel / cnf_rk4_h3w_kernel / conv1x1_x6w_kernel / conv1x1_h3w_kernel" % e, RuntimeWarning)
         run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUT] + objs)
     return OUT
 

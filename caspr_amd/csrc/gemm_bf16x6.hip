@@ -891,15 +891,34 @@ int caspr_conv_x6w_launch(const void *wpk, const float *bias, const float *bbias
                           const float *in_shift, int in_relu, int in_relu_from, float *Y, int ldy, int B, int P, int Cin, int mt_begin, int mt_end,
                           void *part, int part_stride, int reserve_cus, hipStream_t stream) __attribute__((visibility("hidden")));
 
+// the same tiles on three f16 products per f32 product (gemm_f16x3w.hip; config.conv_split = "f16x3")
+int caspr_conv_h3w_launch(const void *wpk, const void *wtail, unsigned *status, const float *bias, const float *bbias, int bb_stride, const float *X, int ldx,
+                          const float *in_scale, const float *in_shift, int in_relu, int in_relu_from, float *Y, int ldy, int B, int P, int Cin, int mt_begin,
+                          int mt_end, void *part, int part_stride, int reserve_cus, hipStream_t stream) __attribute__((visibility("hidden")));
+
+// status != NULL: wpk_main is the pack of caspr_pack_weight_h3w and the 512-channel tiles run on conv1x1_h3w_kernel, whose range guard
+// ORs into *status; the < 512-channel remainder runs on bf16x6 either way
+static int conv_w_main_launch(unsigned *status, const void *wpk, const float *bias, const float *bbias, int bb_stride, const float *X, int ldx,
+                              const float *in_scale, const float *in_shift, int in_relu, int in_relu_from, float *Y, int ldy, int B, int P, int Cin, int Cmain,
+                              int mt_begin, int mt_end, void *part, int part_stride, int reserve_cus, hipStream_t stream)
+{
+    if (!status)
+        return caspr_conv_x6w_launch(wpk, bias, bbias, bb_stride, X, ldx, in_scale, in_shift, in_relu, in_relu_from, Y, ldy, B, P, Cin, mt_begin, mt_end, part,
+                                     part_stride, reserve_cus, stream);
+    const void *wtail = (const unsigned char *)wpk + caspr_h3w_packed_bytes(Cmain, Cin) - 64;
+    return caspr_conv_h3w_launch(wpk, wtail, status, bias, bbias, bb_stride, X, ldx, in_scale, in_shift, in_relu, in_relu_from, Y, ldy, B, P, Cin, mt_begin,
+                                 mt_end, part, part_stride, reserve_cus, stream);
+}
+
 static int conv_x6w_impl(const void *wpk_main, const void *wpk_tail, const float *bias, const float *bbias, const float *X, int ldx,
                          const float *in_scale, const float *in_shift, int in_relu, int in_relu_from, float *Y, int ldy, int B,
                          int P, int Cin, int Cout, int G, int pool, const float *gamma, const float *beta, float eps, float *scale,
-                         float *shift, float *pmax, float *mean, float *rstd, void *ws, long ws_bytes, void *stream)
+                         float *shift, float *pmax, float *mean, float *rstd, void *ws, long ws_bytes, void *stream, unsigned *status = nullptr)
 {
     const int Cmain = Cout - Cout % 512, Ctail = Cout - Cmain;
     CASPR_REQUIRE(wpk_main && X && B > 0 && P > 0 && Cmain >= 512 && (Ctail == 0 || wpk_tail), "conv1x1_x6w: bad arguments (Cout=%d needs >= 512 channels%s)", Cout,
                   Ctail ? " and the bf16x3 pack of the remainder" : "");
-    CASPR_REQUIRE(Cin % 32 == 0 && Cin >= 64 && Cout % 4 == 0 && P % 128 == 0, "conv1x1_x6w: needs Cin %% 32 == 0, Cout %% 4 == 0 and P %% 128 == 0 (Cin=%d Cout=%d P=%d)", Cin, Cout, P);
+    CASPR_REQUIRE(Cin % 32 == 0 && Cin >= (status ? 32 : 64) && Cout % 4 == 0 && P % 128 == 0, "conv1x1_x6w: needs Cin %% 32 == 0, Cout %% 4 == 0 and P %% 128 == 0 (Cin=%d Cout=%d P=%d)", Cin, Cout, P);
     CASPR_REQUIRE(ldx % 4 == 0 && ldx >= Cin && (!Y || (ldy % 4 == 0 && ldy >= Cout)), "conv1x1_x6w: row strides must be multiples of 4 and cover the channels");
     CASPR_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "conv1x1_x6w: in_scale/in_shift must be given together");
     CASPR_REQUIRE(((uintptr_t)X % 16) == 0 && ((uintptr_t)Y % 16) == 0 && ((uintptr_t)wpk_main % 16) == 0 && ((uintptr_t)wpk_tail % 16) == 0 &&
@@ -915,8 +934,8 @@ static int conv_x6w_impl(const void *wpk_main, const void *wpk_tail, const float
     } else {
         CASPR_REQUIRE(Y, "conv1x1_x6w: Y is NULL");
     }
-    int rc = caspr_conv_x6w_launch(wpk_main, bias, bbias, Cout, X, ldx, in_scale, in_shift, in_relu, in_relu_from, Y, ldy, B, P, Cin, 0, Cmain / 512, part,
-                                   Cout, 0, (hipStream_t)stream);
+    int rc = conv_w_main_launch(status, wpk_main, bias, bbias, Cout, X, ldx, in_scale, in_shift, in_relu, in_relu_from, Y, ldy, B, P, Cin, Cmain, 0, Cmain / 512,
+                                part, Cout, 0, (hipStream_t)stream);
     if (rc != CASPR_OK) return rc;
     CASPR_CHECK_LAUNCH("conv1x1_x6w");
     if (Ctail && Ctail <= 64) {
@@ -965,15 +984,15 @@ extern "C" int caspr_conv1x1_x6w_pooled_f32(const void *wpk_main, const void *wp
 //                                   units are left to a kernel of another stream that runs beside it;
 //   caspr_conv_gn_finalize_f32      scale / shift / pmax / mean / rstd of groups g_begin .. g_end - 1 from the partials in ws.
 // Pieces + finalize over all groups == caspr_conv1x1_x6w_f32 / _pooled_f32, bit for bit (tiles and groups are independent).
-extern "C" int caspr_conv1x1_x6w_part_f32(const void *wpk_main, const void *wpk_tail, const float *bias, const float *bbias, const float *X, int ldx,
-                                          const float *in_scale, const float *in_shift, int in_relu, int in_relu_from, float *Y, int ldy, int B,
-                                          int P, int Cin, int Cout, int mt_begin, int mt_end, int with_tail, int reserve_cus, void *ws, long ws_bytes,
-                                          void *stream)
+static int conv_x6w_part_impl(const void *wpk_main, const void *wpk_tail, const float *bias, const float *bbias, const float *X, int ldx,
+                              const float *in_scale, const float *in_shift, int in_relu, int in_relu_from, float *Y, int ldy, int B,
+                              int P, int Cin, int Cout, int mt_begin, int mt_end, int with_tail, int reserve_cus, void *ws, long ws_bytes,
+                              void *stream, unsigned *status)
 {
     const int Cmain = Cout - Cout % 512, Ctail = Cout - Cmain;
     CASPR_REQUIRE(wpk_main && X && B > 0 && P > 0 && Cmain >= 512 && (Ctail == 0 || !with_tail || wpk_tail), "conv1x1_x6w_part: bad arguments");
     CASPR_REQUIRE(mt_begin >= 0 && mt_begin <= mt_end && mt_end <= Cmain / 512, "conv1x1_x6w_part: channel tiles %d..%d of %d", mt_begin, mt_end, Cmain / 512);
-    CASPR_REQUIRE(Cin % 32 == 0 && Cin >= 64 && Cout % 4 == 0 && P % 128 == 0, "conv1x1_x6w_part: needs Cin %% 32 == 0, Cout %% 4 == 0 and P %% 128 == 0");
+    CASPR_REQUIRE(Cin % 32 == 0 && Cin >= (status ? 32 : 64) && Cout % 4 == 0 && P % 128 == 0, "conv1x1_x6w_part: needs Cin %% 32 == 0, Cout %% 4 == 0 and P %% 128 == 0");
     CASPR_REQUIRE(ldx % 4 == 0 && ldx >= Cin && (!Y || (ldy % 4 == 0 && ldy >= Cout)), "conv1x1_x6w_part: row strides must be multiples of 4 and cover the channels");
     CASPR_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "conv1x1_x6w_part: in_scale/in_shift must be given together");
     CASPR_REQUIRE(((uintptr_t)X % 16) == 0 && ((uintptr_t)Y % 16) == 0 && ((uintptr_t)wpk_main % 16) == 0 && ((uintptr_t)wpk_tail % 16) == 0 &&
@@ -984,8 +1003,8 @@ extern "C" int caspr_conv1x1_x6w_part_f32(const void *wpk_main, const void *wpk_
     f32x4 *part = (f32x4 *)ws;
     int rc = CASPR_OK;
     if (mt_end > mt_begin) {
-        rc = caspr_conv_x6w_launch(wpk_main, bias, bbias, Cout, X, ldx, in_scale, in_shift, in_relu, in_relu_from, Y, ldy, B, P, Cin, mt_begin, mt_end, part,
-                                   Cout, reserve_cus, (hipStream_t)stream);
+        rc = conv_w_main_launch(status, wpk_main, bias, bbias, Cout, X, ldx, in_scale, in_shift, in_relu, in_relu_from, Y, ldy, B, P, Cin, Cmain, mt_begin, mt_end,
+                                part, Cout, reserve_cus, (hipStream_t)stream);
         if (rc != CASPR_OK) return rc;
         CASPR_CHECK_LAUNCH("conv1x1_x6w_part");
     }
@@ -996,6 +1015,49 @@ extern "C" int caspr_conv1x1_x6w_part_f32(const void *wpk_main, const void *wpk_
         rc = conv_x6_launch(wpk_tail, bias ? bias + Cmain : nullptr, bbias ? bbias + Cmain : nullptr, X, ldx, in_scale, in_shift, in_relu, in_relu_from,
                             Y ? Y + Cmain : nullptr, ldy, B, P, Cin, Ctail, 0, part + Cmain, stream, Cout);
     return rc;
+}
+
+extern "C" int caspr_conv1x1_x6w_part_f32(const void *wpk_main, const void *wpk_tail, const float *bias, const float *bbias, const float *X, int ldx,
+                                          const float *in_scale, const float *in_shift, int in_relu, int in_relu_from, float *Y, int ldy, int B,
+                                          int P, int Cin, int Cout, int mt_begin, int mt_end, int with_tail, int reserve_cus, void *ws, long ws_bytes,
+                                          void *stream)
+{
+    return conv_x6w_part_impl(wpk_main, wpk_tail, bias, bbias, X, ldx, in_scale, in_shift, in_relu, in_relu_from, Y, ldy, B, P, Cin, Cout, mt_begin, mt_end,
+                              with_tail, reserve_cus, ws, ws_bytes, stream, nullptr);
+}
+
+// ---- the three entries above with the 512-channel tiles on three f16 products per f32 product (gemm_f16x3w.hip): wpk_main is the pack
+// of caspr_pack_weight_h3w, status the word the kernel's range guard ORs into (include/caspr_hip.h); everything else as above
+extern "C" int caspr_conv1x1_h3w_f32(const void *wpk_main, const void *wpk_tail, const float *bias, const float *bbias, const float *X, int ldx,
+                                     const float *in_scale, const float *in_shift, int in_relu, int in_relu_from, float *Y, int ldy, int B,
+                                     int P, int Cin, int Cout, int G, const float *gamma, const float *beta, float eps, float *scale,
+                                     float *shift, float *pmax, float *mean, float *rstd, void *ws, long ws_bytes, unsigned *status, void *stream)
+{
+    CASPR_REQUIRE(status, "conv1x1_h3w: status is NULL");
+    return conv_x6w_impl(wpk_main, wpk_tail, bias, bbias, X, ldx, in_scale, in_shift, in_relu, in_relu_from, Y, ldy, B, P, Cin, Cout, G, 1, gamma, beta,
+                         eps, scale, shift, pmax, mean, rstd, ws, ws_bytes, stream, status);
+}
+
+extern "C" int caspr_conv1x1_h3w_pooled_f32(const void *wpk_main, const void *wpk_tail, const float *bias, const float *bbias, const float *X, int ldx,
+                                            const float *in_scale, const float *in_shift, int in_relu, int in_relu_from, float *Y, int ldy, int B,
+                                            int P, int Cin, int Cout, int G, int pool, const float *gamma, const float *beta, float eps,
+                                            float *scale, float *shift, float *pmax, float *mean, float *rstd, void *ws, long ws_bytes, unsigned *status,
+                                            void *stream)
+{
+    CASPR_REQUIRE(G > 0, "conv1x1_h3w_pooled: needs the GroupNorm statistics (G > 0)");
+    CASPR_REQUIRE(status, "conv1x1_h3w_pooled: status is NULL");
+    return conv_x6w_impl(wpk_main, wpk_tail, bias, bbias, X, ldx, in_scale, in_shift, in_relu, in_relu_from, Y, ldy, B, P, Cin, Cout, G, pool, gamma,
+                         beta, eps, scale, shift, pmax, mean, rstd, ws, ws_bytes, stream, status);
+}
+
+extern "C" int caspr_conv1x1_h3w_part_f32(const void *wpk_main, const void *wpk_tail, const float *bias, const float *bbias, const float *X, int ldx,
+                                          const float *in_scale, const float *in_shift, int in_relu, int in_relu_from, float *Y, int ldy, int B,
+                                          int P, int Cin, int Cout, int mt_begin, int mt_end, int with_tail, int reserve_cus, void *ws, long ws_bytes,
+                                          unsigned *status, void *stream)
+{
+    CASPR_REQUIRE(status, "conv1x1_h3w_part: status is NULL");
+    return conv_x6w_part_impl(wpk_main, wpk_tail, bias, bbias, X, ldx, in_scale, in_shift, in_relu, in_relu_from, Y, ldy, B, P, Cin, Cout, mt_begin, mt_end,
+                              with_tail, reserve_cus, ws, ws_bytes, stream, status);
 }
 
 extern "C" int caspr_conv_gn_finalize_f32(const void *ws, long ws_bytes, int B, int P, int Cout, int G, int g_begin, int g_end, int pool,

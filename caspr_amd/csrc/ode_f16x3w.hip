@@ -25,37 +25,21 @@
 //    barrier in its last region; that barrier waits with vmcnt(24): the six younger pieces may still be in flight;
 //  * a region is one k-step x two row tiles = 6 MFMAs, one scheduling slot each; slots 0-3 read the next region's four fragments; the
 //    producers run two micro-steps per slot in pass 0 of layer 2 (the same work per k-step under half the MFMAs).
-#include "x6w_common.h"
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 xh_f16x2 __attribute__((ext_vector_type(2)));
+#include "f16x3_common.h"
 
 #define XH_PTS 128
 #define XH_FRAG 1024                      // one A fragment of v_mfma_f32_32x32x16_f16: 64 lanes x 16 B
 #define XH_PIECE (2 * 4 * 2 * XH_FRAG)    // 16 KB: [k-step 2][row tile 4][plane 2][fragment]
 #define XH_PACK (4L * 16 * XH_PIECE)      // one hidden layer: [row quarter 4][k chunk 16][piece] = 1 MB
-#define XH_TAIL 64                        // behind the pack: int shift s (weights were multiplied by 2^s), unsigned bits of max |W|
 #define XH_RING 8
 #define XH_TAB (XH_RING * XH_PIECE)
 // tables (floats): hb0[512] w0g[3][512] g1[512] hb1[512] g2[512] hb2[512] w3[3][512] w0[512][3] g3[8]
 #define XH_TAB_FLOATS (14 * XC_H + 8)
 #define XH_LDS (XH_TAB + XH_TAB_FLOATS * 4)
-#define XH_ACT_SHIFT 4
-#define XH_F16_LIMIT 65520.0f             // the smallest f32 that rounds to inf in f16
-#define XH_FLUSH 0x1.ffcp-15f             // 2^-14 - 2^-25: below it rne16 gives a subnormal (at it, a tie, 2^-14)
 
 struct CnfH3Args : CnfX6Args {
     unsigned *status;                     // one word per launch, zeroed in front of it: != 0 <-> the range guard tripped
 };
-
-template <int T, bool NOPS>
-__device__ __forceinline__ void xh_mfma_a(f16x8 af, f16x8 bf)
-{
-    if constexpr (NOPS)
-        asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_f16 a[%c2:%c3], %0, %1, a[%c2:%c3]" : : "v"(af), "v"(bf), "i"(16 * T), "i"(16 * T + 15) : XW_ACLOB);
-    else
-        asm volatile("v_mfma_f32_32x32x16_f16 a[%c2:%c3], %0, %1, a[%c2:%c3]" : : "v"(af), "v"(bf), "i"(16 * T), "i"(16 * T + 15) : XW_ACLOB);
-}
 
 // ---- softplus on the scaled value X = 16 x, and the two-plane split, in micro-steps (XwPair of x6w_common.h) ----
 __device__ __forceinline__ void xh_sp1(XwPair &p)     // u = 2^(-|x| log2 e), x = X / 16
@@ -69,11 +53,6 @@ __device__ __forceinline__ void xh_sp3(XwPair &p, float &xmax)     // X = max(X,
     p.x1 = fmaxf(p.x1, 0.0f) + 11.090354888959125f * p.u1;
     // (as asm: left to hipcc, the maxima are re-associated and sunk to the end of the stage, every X of the stage kept live for them)
     asm volatile("v_max3_f32 %0, %0, %1, %2" : "+v"(xmax) : "v"(p.x0), "v"(p.x1));
-}
-__device__ __forceinline__ unsigned xh_cvt_pk(float lo, float hi)
-{
-    const xc_f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, xh_f16x2));
 }
 __device__ __forceinline__ void xh_split1(XwPair &p)  // first plane (flushed) + remainder; X >= 0 here
 {
@@ -584,16 +563,7 @@ __global__ void h3_weight_max_kernel(const float *__restrict__ w, int ldw, unsig
     for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
     if ((threadIdx.x & 63) == 0) atomicMax(tail + 1, m);
 }
-// the shift s that puts max |W| 2^s in [2^14, 2^15): 14 - floor(log2 max); 0 for an all-zero, subnormal or non-finite layer.  Clamped at
-// XH_MAX_SHIFT so that the unscale factors 2^-s and 2^-(4 + s) the kernel folds into its gate tables stay NORMAL f32 numbers (a gate times
-// a subnormal factor would flush and the layer would put out its bias alone): a layer whose max |W| is below 2^-86 keeps shift 100 and
-// loses residual-plane bits instead -- its whole product is below 512 x 4095 x 2^-86 = 3e-20, absolute
-#define XH_MAX_SHIFT 100
-__device__ __forceinline__ int h3_shift(unsigned maxbits)
-{
-    const int e = (int)(maxbits >> 23);
-    return (e == 0 || e == 255) ? 0 : min(14 - (e - 127), XH_MAX_SHIFT);
-}
+// (h3_shift: f16x3_common.h)
 __global__ void pack_weight_cnf_h3_kernel(const float *__restrict__ w, int ldw, unsigned char *__restrict__ out)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;   // ((rq * 16 + kc) * 8 + ks * 4 + rt) * 64 + lane

@@ -261,6 +261,17 @@ CNF_SPLIT = _cfg.cnf_split           # "f16x3": the sampling solve (no divergenc
                                      # matmul_mode()["cnf"] says "bf16x6" for both (the family; bench.py keys its roofline block on that string)
 
 
+CONV_SPLIT = _cfg.conv_split         # "f16x3": the layers of the persistent 512-channel conv on three f16 products per f32 product (csrc/gemm_f16x3w.hip),
+                                     # inference only; matmul_mode()["conv"] says "bf16x6" for both (the family), the timer keys stay what they are
+
+
+def conv_split():
+    """CONV_SPLIT, validated where it is read (a run-time switch: a misspelt value must not select bf16x6 silently)."""
+    if CONV_SPLIT not in ("bf16x6", "f16x3"):
+        raise ValueError("caspr_amd.ops.CONV_SPLIT must be 'bf16x6' or 'f16x3', got %r" % (CONV_SPLIT,))
+    return CONV_SPLIT
+
+
 def cnf_split():
     """CNF_SPLIT, validated where it is read: the attribute is a run-time switch, and a misspelt value must not select bf16x6 silently."""
     if CNF_SPLIT not in ("bf16x6", "f16x3"):
@@ -323,6 +334,7 @@ class PackedWeight:
         self.x6_gn_ok = self.cin % 32 == 0 and self.cin >= _X6_GN_MIN_CIN and self.cout % 4 == 0 and self.cout >= 128
         self._x3 = None
         self._xw = None
+        self._xh = None
         # the 128-point x 512-channel kernel (csrc/gemm_bf16x6w.hip) takes the layers with >= 512 output channels and >= 8 k chunks
         self.x6w_ok = self.cin % 32 == 0 and self.cin >= _X6W_MIN_CIN and self.cout % 4 == 0 and self.cout >= 512
         # kept for the lazy bf16x3 pack only, with the version the f32 pack was taken at: w2d may be a VIEW of a parameter
@@ -339,7 +351,7 @@ class PackedWeight:
             self._x3 = torch.empty(nbytes, device=w2d.device, dtype=torch.uint8)
             _lib.check(_lib.load().caspr_pack_weight_bf16x3(_p(w2d), ldw, self.cout, col0, self.cin, _p(self._x3), _stream()),
                        "caspr_pack_weight_bf16x3")
-            if not self.x6w_ok or self._xw is not None:
+            if not self.x6w_ok or (self._xw is not None and self._xh is not None):
                 self._src = None        # every pack exists: release the (possibly padded) copy of the weight
         return self._x3
 
@@ -360,15 +372,134 @@ class PackedWeight:
                 tail = torch.empty(L.caspr_bf16x3_packed_bytes(self.cout - cmain, self.cin), device=w2d.device, dtype=torch.uint8)
                 _lib.check(L.caspr_pack_weight_bf16x3(_p(wt), ldw, self.cout - cmain, col0, self.cin, _p(tail), _stream()), "caspr_pack_weight_bf16x3")
             self._xw = (main, tail)
-            if self._x3 is not None:
+            if self._x3 is not None and self._xh is not None:
                 self._src = None
         return self._xw
+
+    def xh(self):
+        """(main, tail) packs of caspr_conv1x1_h3w_f32 (conv_split = "f16x3"): the first cout - cout % 512 rows as two f16 planes with
+        the layer's power-of-two scale behind them (found on the device: no host synchronisation), the rest (or None) as the bf16x3
+        pack of xw() -- the remainder stays on bf16x6.  Built on first use from the same source, under the same version check."""
+        if self._xh is None:
+            w2d, ldw, col0, version = self._src
+            if w2d._version != version:
+                raise RuntimeError("PackedWeight.xh(): the weight tensor was modified in place after this pack was built")
+            L = _lib.load()
+            cmain = self.cout - self.cout % 512
+            main = torch.empty(L.caspr_h3w_packed_bytes(cmain, self.cin), device=w2d.device, dtype=torch.uint8)
+            _lib.check(L.caspr_pack_weight_h3w(_p(w2d), ldw, cmain, col0, self.cin, _p(main), _stream()), "caspr_pack_weight_h3w")
+            tail = None
+            if cmain != self.cout:
+                if self._xw is not None:
+                    tail = self._xw[1]
+                else:
+                    wt = w2d[cmain:]
+                    tail = torch.empty(L.caspr_bf16x3_packed_bytes(self.cout - cmain, self.cin), device=w2d.device, dtype=torch.uint8)
+                    _lib.check(L.caspr_pack_weight_bf16x3(_p(wt), ldw, self.cout - cmain, col0, self.cin, _p(tail), _stream()), "caspr_pack_weight_bf16x3")
+            self._xh = (main, tail)
+            if self._x3 is not None and self._xw is not None:
+                self._src = None
+        return self._xh
 
 
 CONV_ROW_INVARIANT = 0x100     # include/caspr_hip.h: act flag
 
 
-def conv1x1(pw, bias, x, bbias=None, in_scale=None, in_shift=None, in_relu=False, in_relu_from=0, act=0, out=None, row_invariant=False):
+# The f16x3 conv's range guard (csrc/gemm_f16x3w.hip): an input value that is not finite in f16 after the 2^4 scale makes its row NaN and
+# ORs into a status word.  One word per (device, stream), never cleared by a launch: it is copied to pinned host memory behind a conv when
+# no earlier copy is still outstanding (eight wide layers per encoder pass would otherwise queue eight copies), read when that copy has
+# arrived -- at the next f16x3 conv on the stream, or by check_deferred_errors, which first fetches what the skipped copies would have
+# shown -- and cleared once it has been reported.
+_c3_status = {}          # stream key -> [(pinned host tensor, event)], at most one
+_c3_pool = []
+_c3_word = {}            # stream key -> (device word, the torch stream it belongs to)
+_c3_stale = set()        # stream keys with launches behind the last copy
+CONV_ROUTE_COUNT = {"h3w": 0}      # launches of the f16x3 entries so far (tests assert the route from it)
+
+
+def _c3_raise_if_failed(key, wait=False):
+    ring = _c3_status.get(key)
+    failed = False
+    while ring:
+        host, ev = ring[0]
+        if wait:
+            ev.synchronize()
+        if not ev.query():
+            break
+        ring.pop(0)
+        failed = failed or int(host[0]) != 0
+        _c3_pool.append(host)
+    if failed:
+        word, stream = _c3_word[key]
+        with torch.cuda.stream(stream):
+            word.zero_()                               # reported: the next call starts clean
+        raise _lib.CasprHipError("caspr_conv1x1_h3w_f32: the range guard of the f16x3 pointwise conv tripped: an input activation (after the "
+                                 "producer's GroupNorm / ReLU) reached 4095 in magnitude or was not finite, which f16 cannot hold after the kernel's "
+                                 "2^4 prescale; the outputs of the affected rows were set to NaN.  Remedy: conv_split=\"bf16x6\" "
+                                 "(caspr_amd.config.config.conv_split / caspr_amd.ops.CONV_SPLIT), the six-product bf16 kernel, which has f32's "
+                                 "exponent range")
+
+
+def _c3_fetch(key):
+    word, stream = _c3_word[key]
+    host = _c3_pool.pop() if _c3_pool else torch.zeros(1, dtype=torch.int32).pin_memory()
+    ev = torch.cuda.Event()
+    with torch.cuda.stream(stream):
+        host.copy_(word, non_blocking=True)
+        ev.record(stream)
+    _c3_status.setdefault(key, []).append((host, ev))
+    _c3_stale.discard(key)
+
+
+def _c3_drain(key, wait=False):
+    if wait and key in _c3_stale and not _c3_status.get(key):
+        _c3_fetch(key)
+    _c3_raise_if_failed(key, wait=wait)
+    if wait and key in _c3_stale:                      # launches behind the copy that was outstanding
+        _c3_fetch(key)
+        _c3_raise_if_failed(key, wait=True)
+
+
+class _c3_launch:
+    """with _c3_launch(x) as word: <launch an f16x3 conv that ORs into word>  -- reports an earlier launch's trip first (never under
+    stream capture: no event queries, no host copies there)."""
+
+    def __init__(self, x):
+        self.dev = x.device
+
+    def __enter__(self):
+        stream = torch.cuda.current_stream()
+        self.key = (self.dev.index, stream.cuda_stream)
+        self.capturing = torch.cuda.is_current_stream_capturing()
+        if not self.capturing:
+            _c3_raise_if_failed(self.key)
+        CONV_ROUTE_COUNT["h3w"] += 1
+        ent = _c3_word.get(self.key)
+        if ent is None:
+            ent = _c3_word[self.key] = (torch.zeros(1, device=self.dev, dtype=torch.int32), stream)
+        return _p(ent[0])
+
+    def __exit__(self, *exc):
+        if exc[0] is None and not self.capturing:
+            if _c3_status.get(self.key):
+                _c3_stale.add(self.key)
+            else:
+                _c3_fetch(self.key)
+        return False
+
+
+def _conv_h3w(split):
+    """Does a layer that takes the persistent 512-channel kernel run on its f16x3 form?  split: None = CONV_SPLIT; the training tier
+    passes "bf16x6" (conv1x1_train, conv1x1_gn(split=)): its forward, backward and tapes keep the bits they had."""
+    return (conv_split() if split is None else split) == "f16x3"
+
+
+def conv1x1_train(*args, **kwargs):
+    """conv1x1 for the training tier (train/encoder_grad.py, train/flow_grad.py): always the bf16x6 / f32 kernels, whatever CONV_SPLIT says."""
+    return conv1x1(*args, split="bf16x6", **kwargs)
+
+
+def conv1x1(pw, bias, x, bbias=None, in_scale=None, in_shift=None, in_relu=False, in_relu_from=0, act=0, out=None, row_invariant=False, split=None):
     """Pointwise conv on MFMA: x (B,P,>=Cin) point-major (may be a column slice of a wider buffer) ->
     (B,P,roundup4(Cout)) or into `out` (same rules).  See caspr_conv1x1_f32.
     row_invariant: a row's result depends on that row only (not on P / its position): for convs over frames-as-rows."""
@@ -383,6 +514,13 @@ def conv1x1(pw, bias, x, bbias=None, in_scale=None, in_shift=None, in_relu=False
         out = torch.empty(B, P, (pw.cout + 3) // 4 * 4, device=x.device, dtype=torch.float32)
     ldy = _chk_rows(out)
     if CONV_BF16X6 and CONV_X6W and pw.x6w_ok and P % 128 == 0 and not row_invariant and in_relu_from % 8 == 0 and act == 0 and _x6w_fills(pw, B, P):
+        if _conv_h3w(split):
+            main, tail = pw.xh()
+            with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, pw.cout, B * P), 2), _c3_launch(x) as word:
+                _lib.check(_lib.load().caspr_conv1x1_h3w_f32(_p(main), _p(tail), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
+                                                             int(in_relu_from), _p(out), ldy, B, P, pw.cin, pw.cout, 0, None, None, 0.0, None, None, None,
+                                                             None, None, None, 0, word, _stream()), "caspr_conv1x1_h3w_f32")
+            return out
         main, tail = pw.xw()
         with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, pw.cout, B * P), 2):
             _lib.check(_lib.load().caspr_conv1x1_x6w_f32(_p(main), _p(tail), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
@@ -429,7 +567,7 @@ def gn_stats(y, C, gamma, beta, groups=16, eps=1e-5, want_max=False):
 
 
 def conv1x1_gn(pw, bias, x, gamma, beta, groups=16, eps=1e-5, want_max=False, want_moments=False, write=True, bbias=None,
-               in_scale=None, in_shift=None, in_relu=False, in_relu_from=0, out=None, pool=1):
+               in_scale=None, in_shift=None, in_relu=False, in_relu_from=0, out=None, pool=1, split=None):
     """conv1x1 followed by the statistics of the GroupNorm on its output (the model's conv -> GroupNorm -> ReLU block):
     -> (y | None, scale (B,C), shift (B,C)[, mean (B,G), rstd (B,G)][, pmax (B,C)]).  On the bf16x6 path the statistics come
     out of the conv's epilogue (caspr_conv1x1_gn_bf16x6_f32) and `write=False` skips the output altogether; otherwise this is
@@ -442,7 +580,7 @@ def conv1x1_gn(pw, bias, x, gamma, beta, groups=16, eps=1e-5, want_max=False, wa
     if pool < 1 or B % pool:
         raise ValueError("conv1x1_gn: pool=%d must divide the %d batch entries" % (pool, B))
     if not (CONV_BF16X6 and pw.x6_gn_ok and P % 128 == 0 and C % groups == 0 and in_relu_from % 8 == 0):
-        y = conv1x1(pw, bias, x, bbias=bbias, in_scale=in_scale, in_shift=in_shift, in_relu=in_relu, in_relu_from=in_relu_from, out=out)
+        y = conv1x1(pw, bias, x, bbias=bbias, in_scale=in_scale, in_shift=in_shift, in_relu=in_relu, in_relu_from=in_relu_from, out=out, split=split)
         yg = y.view(B // pool, pool * P, y.shape[2]) if pool > 1 else y
         if want_moments:
             from . import train_ops
@@ -464,6 +602,20 @@ def conv1x1_gn(pw, bias, x, gamma, beta, groups=16, eps=1e-5, want_max=False, wa
     pmax = torch.empty(Bs, C, device=dev, dtype=torch.float32) if want_max else None
     L = _lib.load()
     ws = _workspace(L.caspr_conv_gn_ws_bytes(B, P, C), dev)
+    h3w = _conv_h3w(split)
+    if pool > 1 and CONV_X6W and pw.x6w_ok and _x6w_fills(pw, B, P) and h3w:
+        main, tail = pw.xh()
+        with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, C, B * P), 2), _c3_launch(x) as word:
+            _lib.check(L.caspr_conv1x1_h3w_pooled_f32(_p(main), _p(tail), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
+                                                      int(in_relu_from), _p(y), ldy, B, P, pw.cin, C, groups, int(pool), _p(gamma), _p(beta), float(eps),
+                                                      _p(scale), _p(shift), _p(pmax), _p(mean), _p(rstd), _p(ws), ws.numel(), word, _stream()),
+                       "caspr_conv1x1_h3w_pooled_f32")
+        res = (y, scale, shift)
+        if want_moments:
+            res += (mean, rstd)
+        if want_max:
+            res += (pmax,)
+        return res
     if pool > 1 and CONV_X6W and pw.x6w_ok and _x6w_fills(pw, B, P):
         main, tail = pw.xw()
         with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, C, B * P), 2):
@@ -483,6 +635,19 @@ def conv1x1_gn(pw, bias, x, gamma, beta, groups=16, eps=1e-5, want_max=False, wa
                                                             int(in_relu_from), _p(y), ldy, B, P, pw.cin, C, groups, int(pool), _p(gamma), _p(beta),
                                                             float(eps), _p(scale), _p(shift), _p(pmax), _p(mean), _p(rstd), _p(ws), ws.numel(),
                                                             _stream()), "caspr_conv1x1_gn_pooled_bf16x6_f32")
+        res = (y, scale, shift)
+        if want_moments:
+            res += (mean, rstd)
+        if want_max:
+            res += (pmax,)
+        return res
+    if CONV_X6W and pw.x6w_ok and _x6w_fills(pw, B, P) and h3w:
+        main, tail = pw.xh()
+        with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, C, B * P), 2), _c3_launch(x) as word:
+            _lib.check(L.caspr_conv1x1_h3w_f32(_p(main), _p(tail), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
+                                               int(in_relu_from), _p(y), ldy, B, P, pw.cin, C, groups, _p(gamma), _p(beta), float(eps),
+                                               _p(scale), _p(shift), _p(pmax), _p(mean), _p(rstd), _p(ws), ws.numel(), word, _stream()),
+                       "caspr_conv1x1_h3w_f32")
         res = (y, scale, shift)
         if want_moments:
             res += (mean, rstd)
@@ -548,10 +713,17 @@ def conv1x1_gn_early(pw, bias, x, gamma, beta, on_early, groups=16, eps=1e-5, in
     pmax = torch.empty(B, C, device=dev, dtype=torch.float32)
     L = _lib.load()
     ws = _workspace(L.caspr_conv_gn_ws_bytes(B, P, C), dev)
-    main, tail = pw.xw()
+    h3w = _conv_h3w(None)
+    main, tail = pw.xh() if h3w else pw.xw()
     mt_all = C // 512
 
     def part(mt0, mt1, with_tail, reserve):
+        if h3w:
+            with _c3_launch(x) as word:
+                _lib.check(L.caspr_conv1x1_h3w_part_f32(_p(main), _p(tail), _p(bias), None, _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
+                                                        int(in_relu_from), _p(y), ldy, B, P, pw.cin, C, mt0, mt1, int(with_tail), int(reserve), _p(ws),
+                                                        ws.numel(), word, _stream()), "caspr_conv1x1_h3w_part_f32")
+            return
         _lib.check(L.caspr_conv1x1_x6w_part_f32(_p(main), _p(tail), _p(bias), None, _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu), int(in_relu_from),
                                                 _p(y), ldy, B, P, pw.cin, C, mt0, mt1, int(with_tail), int(reserve), _p(ws), ws.numel(), _stream()),
                    "caspr_conv1x1_x6w_part_f32")
@@ -607,10 +779,17 @@ def conv1x1_gn_tail_beside(pw, bias, x, gamma, beta, tail_stream, groups=16, eps
     shift = torch.empty(Bs, C, device=dev, dtype=torch.float32)
     L = _lib.load()
     ws = _workspace(L.caspr_conv_gn_ws_bytes(B, P, C), dev)
-    main, tail = pw.xw()
+    h3w = _conv_h3w(None)
+    main, tail = pw.xh() if h3w else pw.xw()
     mt_all = C // 512
 
     def part(mt0, mt1, with_tail):
+        if h3w:
+            with _c3_launch(x) as word:
+                _lib.check(L.caspr_conv1x1_h3w_part_f32(_p(main), _p(tail), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
+                                                        int(in_relu_from), _p(y), ldy, B, P, pw.cin, C, mt0, mt1, int(with_tail), 0, _p(ws), ws.numel(),
+                                                        word, _stream()), "caspr_conv1x1_h3w_part_f32")
+            return
         _lib.check(L.caspr_conv1x1_x6w_part_f32(_p(main), _p(tail), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu), int(in_relu_from),
                                                 _p(y), ldy, B, P, pw.cin, C, mt0, mt1, int(with_tail), 0, _p(ws), ws.numel(), _stream()),
                    "caspr_conv1x1_x6w_part_f32")
@@ -752,7 +931,7 @@ def _team_raise_if_failed(key, wait=False):
 
 def check_deferred_errors(wait=True):
     """Raise CasprHipError if an earlier asynchronous kernel reported a failure (the latent team kernel's barrier, the adaptive
-    latent solve's attempt budget, the range guard of the f16x3 CNF solve, a frame capped by the per-frame step controller), or
+    latent solve's attempt budget, the range guard of the f16x3 CNF solve or of the f16x3 convs, a frame capped by the per-frame step controller), or
     CasprAccuracyError / warn if a run-time accuracy check of the fixed-step integrators came back above its tolerance
     (guard_track).  wait=True blocks until the status words of every outstanding solve / check have arrived."""
     for key in list(_team_status):
@@ -761,6 +940,8 @@ def check_deferred_errors(wait=True):
         _dp5_raise_if_failed(key, wait=wait)
     for key in list(_h3_status):
         _h3_raise_if_failed(key, wait=wait)
+    for key in list(_c3_word):
+        _c3_drain(key, wait=wait)
     for key in list(_steps_status):
         _steps_raise_if_capped(key, wait=wait)
     _guard_drain(wait=wait)

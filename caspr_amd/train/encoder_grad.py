@@ -67,7 +67,7 @@ def _conv_gn_fwd(packs, conv, gn, cur, want_max=False, out=None, bbias=None, pw=
     C = conv.out_channels
     res = ops.conv1x1_gn(pw if pw is not None else packs.fwd(conv), conv.bias if bias == "conv" else None, cur.raw, gn.weight, gn.bias,
                          want_max=want_max, want_moments=True, bbias=bbias, in_scale=cur.scale, in_shift=cur.shift, in_relu=cur.relu,
-                         in_relu_from=in_relu_from, out=out)
+                         in_relu_from=in_relu_from, out=out, split="bf16x6")
     y, st = res[0], res[1:]
     rec = {"x": cur, "y": y, "mean": st[2], "rstd": st[3], "conv": conv, "gn": gn, "scale": st[0], "shift": st[1]}
     return Lazy(y, C, st[0], st[1], True), rec, (st[4] if want_max else None)
@@ -85,7 +85,7 @@ def _conv_gn_bwd(packs, grads, rec, da, relu=True, dmax=None, amax=None, need_dx
     T.conv1x1_wgrad(dy, x.raw, cin, C, dW, dbias, in_scale=x.scale, in_shift=x.shift, in_relu=x.relu)
     if not need_dx:
         return None
-    return ops.conv1x1(packs.bwd(conv), None, dy)
+    return ops.conv1x1_train(packs.bwd(conv), None, dy)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -101,7 +101,7 @@ def _sa_scale_fwd(packs, pn, xyz, new_xyz, feat, C, idx, out, off, need_input_gr
     recs = []
     n_layers = len(pn.conv_layers)
     for l, (conv, gn) in enumerate(zip(pn.conv_layers, pn.bn_layers)):
-        y = ops.conv1x1(packs.fwd(conv), conv.bias, cur)
+        y = ops.conv1x1_train(packs.fwd(conv), conv.bias, cur)
         last = l == n_layers - 1
         Cl = conv.out_channels
         A, mean, rstd, arg = T.gn_rows(y, ns, Cl, gn.weight, gn.bias, relu=not last, maxout=out[:, :, off:off + Cl] if last else None)
@@ -133,7 +133,7 @@ def _sa_scale_bwd(packs, grads, rec, dout, dfeat):
         dW, dbias = grads.conv(conv)
         T.conv1x1_wgrad(dy, r["x"], conv.in_channels, Cl, dW, dbias)
         if l > 0 or dfeat is not None:
-            d = ops.conv1x1(packs.bwd(conv), None, dy)
+            d = ops.conv1x1_train(packs.bwd(conv), None, dy)
     if dfeat is not None:
         T.segment_sum(d, rec["seg"], rec["C"], dfeat, col0=3, accumulate=True)     # fixed-order form of group_rows_bwd
 
@@ -212,7 +212,7 @@ def encoder_forward(enc, x):
         target -= 1
     c0, gnf, c3 = pn2.final_layers[0], pn2.final_layers[1], pn2.final_layers[3]
     af, rf, _ = _conv_gn_fwd(packs, c0, gnf, prev)
-    ops.conv1x1(packs.fwd(c3), c3.bias, af.raw, in_scale=af.scale, in_shift=af.shift, in_relu=True, out=X1.view(B * T_, N, L + S)[:, :, :L])
+    ops.conv1x1_train(packs.fwd(c3), c3.bias, af.raw, in_scale=af.scale, in_shift=af.shift, in_relu=True, out=X1.view(B * T_, N, L + S)[:, :, :L])
     tape.final = (rf, af, c3)
     tape.sa_shapes = [(f.shape[1], f.shape[2]) for f in feat_list[1:]]
 
@@ -225,7 +225,7 @@ def encoder_forward(enc, x):
         w_g = w2[:, L:L + Gf].contiguous()
         return ops.PackedWeight(w_pt), ops.PackedWeight(w_g), ops.PackedWeight(w_pt.t().contiguous()), ops.PackedWeight(w_g.t().contiguous())
     w_pt, w_g, w_pt_t, w_g_t = packs.get((id(enc.conv1), "head"), w, build_head)
-    bbias = ops.conv1x1(w_g, enc.conv1.bias, gmax.view(B, 1, -1)).view(B, -1)
+    bbias = ops.conv1x1_train(w_g, enc.conv1.bias, gmax.view(B, 1, -1)).view(B, -1)
     ones = torch.ones(B, L, device=dev, dtype=torch.float32)
     in_scale = torch.cat([ones, a1.scale], dim=1).contiguous()
     in_shift = torch.cat([torch.zeros_like(ones), a1.shift], dim=1).contiguous()
@@ -234,7 +234,7 @@ def encoder_forward(enc, x):
     h2, rh2, z0 = _conv_gn_fwd(packs, enc.conv2, enc.bn2, h1, want_max=True)
     tnocs, t_full = None, None
     if enc.regress_tnocs:
-        t_full = ops.conv1x1(packs.fwd(enc.conv3), enc.conv3.bias, h2.raw, in_scale=h2.scale, in_shift=h2.shift, in_relu=True, act=1)
+        t_full = ops.conv1x1_train(packs.fwd(enc.conv3), enc.conv3.bias, h2.raw, in_scale=h2.scale, in_shift=h2.shift, in_relu=True, act=1)
         tnocs = t_full[:, :, :enc.tnocs_point_size].reshape(B, T_, N, enc.tnocs_point_size)
     tape.head = (rh1, rh2, h2, t_full, gmax, (w_pt_t, w_g_t))
     tape.dims = (B, T_, N, L, S, Gf)
@@ -262,7 +262,7 @@ def encoder_backward(enc, tape, dz0, dtnocs):
         dy3[:, :, :k] = dtnocs.reshape(B, P, k).float() * t * (1.0 - t)            # sigmoid' (tpointnet2.py:106)
         dW3, db3 = grads.conv(enc.conv3)
         T.conv1x1_wgrad(dy3, h2.raw, F_, k, dW3, db3, in_scale=h2.scale, in_shift=h2.shift, in_relu=True)
-        da2 = ops.conv1x1(packs.bwd(enc.conv3), None, dy3)
+        da2 = ops.conv1x1_train(packs.bwd(enc.conv3), None, dy3)
     elif enc.regress_tnocs:
         grads.new(enc.conv3.weight).zero_()
         grads.new(enc.conv3.bias).zero_()
@@ -291,8 +291,8 @@ def encoder_backward(enc, tape, dz0, dtnocs):
     gw1[:, :L] = dWpt[:, :L]
     gw1[:, L:L + Gf] = dWg
     gw1[:, L + Gf:] = dWpt[:, L:]
-    dgmax = ops.conv1x1(w_g_t, None, dbb.view(B, 1, C1)).view(B, -1)[:, :Gf].contiguous()
-    dX1 = ops.conv1x1(w_pt_t, None, dy1)                                            # (B,P,L+S): [d local | d point feature]
+    dgmax = ops.conv1x1_train(w_g_t, None, dbb.view(B, 1, C1)).view(B, -1)[:, :Gf].contiguous()
+    dX1 = ops.conv1x1_train(w_pt_t, None, dy1)                                            # (B,P,L+S): [d local | d point feature]
     del dy1, da1
 
     # ---- global PointNet ----
@@ -313,7 +313,7 @@ def encoder_backward(enc, tape, dz0, dtnocs):
     dlocal = dX1.view(B * T_, N, L + S)[:, :, :L]
     dW, dbias = grads.conv(c3)
     T.conv1x1_wgrad(dlocal, af.raw, c3.in_channels, c3.out_channels, dW, dbias, in_scale=af.scale, in_shift=af.shift, in_relu=True)
-    daf = ops.conv1x1(packs.bwd(c3), None, dlocal)
+    daf = ops.conv1x1_train(packs.bwd(c3), None, dlocal)
     dprev = _conv_gn_bwd(packs, grads, rf, daf, relu=True)
     del daf, dX1
     dsa = [torch.zeros(B * T_, m, c, device=dev, dtype=torch.float32) for (m, c) in tape.sa_shapes]

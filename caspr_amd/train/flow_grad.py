@@ -56,7 +56,7 @@ class LinearRows(torch.autograd.Function):
             raise ValueError("LinearRows runs on the GPU only (HIP kernels)")
         cout, cin = w.shape
         xp = _pad4(x[:, :cin]) if x.shape[1] != (cin + 3) // 4 * 4 else x.contiguous()
-        y = ops.conv1x1(_packed(w, False), None if b is None else b.detach().contiguous(), xp.view(1, xp.shape[0], xp.shape[1]))
+        y = ops.conv1x1_train(_packed(w, False), None if b is None else b.detach().contiguous(), xp.view(1, xp.shape[0], xp.shape[1]))
         ctx.save_for_backward(xp, w)
         ctx.has_bias = b is not None
         ctx.x_cols = x.shape[1]
@@ -71,7 +71,7 @@ class LinearRows(torch.autograd.Function):
         dyv = dyp.view(1, R, dyp.shape[1])
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx = ops.conv1x1(_packed(w, True), None, dyv).view(R, -1)
+            dx = ops.conv1x1_train(_packed(w, True), None, dyv).view(R, -1)
             if dx.shape[1] != cin:
                 dx[:, cin:] = 0.0
             if dx.shape[1] != ctx.x_cols:
@@ -159,7 +159,7 @@ class CnfLayer(torch.autograd.Function):
         _lib.check(_lib.load().caspr_cnf_act_bwd_f32(_p(z), cout, _p(b), _p(gate), _p(beta), _p(dh), cout, R2 // 2, ctx.n, cout, 32, _p(dz), cout,
                                                      _p(dgate), _p(dbeta), _stream()), "caspr_cnf_act_bwd_f32")
         dzv = dz.view(1, R2, cout)
-        dx = ops.conv1x1(_packed(w, True), None, dzv).view(R2, -1) if ctx.needs_input_grad[0] else None
+        dx = ops.conv1x1_train(_packed(w, True), None, dzv).view(R2, -1) if ctx.needs_input_grad[0] else None
         dw = torch.empty(cout, cin, device=xp.device, dtype=torch.float32)
         T.conv1x1_wgrad(dzv, xp.view(1, R2, cin), cin, cout, dw, None)
         return dx, dw, (gate * dbeta).sum(dim=0), dgate, dbeta, None
@@ -184,7 +184,7 @@ class CnfLayerOut(torch.autograd.Function):
         with ops.timed("k:conv1x1_bf16x6:%d:%d:%d" % (cin, cout, R2), 2):
             _lib.check(_lib.load().caspr_conv1x1_cnf_act_bf16x6_f32(_p(_packed(w, False).x3()), _p(b), _p(gate), _p(beta), _p(xp), xp.stride(0), _p(z), cout,
                                                                     _p(h), cout, R2 // (2 * n), n, cin, cout, _stream()), "caspr_conv1x1_cnf_act_bf16x6_f32")
-        zo = ops.conv1x1(_packed(wo, False), None, h.view(1, R2, cout)).view(R2, -1)
+        zo = ops.conv1x1_train(_packed(wo, False), None, h.view(1, R2, cout)).view(R2, -1)
         ctx.save_for_backward(xp, w, z, b, gate, beta, h, wo)
         ctx.n = n
         return zo[:, :wo.shape[0]]
@@ -205,7 +205,7 @@ class CnfLayerOut(torch.autograd.Function):
         _lib.check(_lib.load().caspr_cnf_act_bwd_out_f32(_p(z), cout, _p(b), _p(gate), _p(beta), _p(dzop), dzop.shape[1], _p(woc), cout, R2 // 2, ctx.n, cout,
                                                          32, _p(dz), cout, _p(dgate), _p(dbeta), _stream()), "caspr_cnf_act_bwd_out_f32")
         dzv = dz.view(1, R2, cout)
-        dx = ops.conv1x1(_packed(w, True), None, dzv).view(R2, -1) if ctx.needs_input_grad[0] else None
+        dx = ops.conv1x1_train(_packed(w, True), None, dzv).view(R2, -1) if ctx.needs_input_grad[0] else None
         dw = torch.empty(cout, cin, device=xp.device, dtype=torch.float32)
         T.conv1x1_wgrad(dzv, xp.view(1, R2, cin), cin, cout, dw, None)
         return dx, dw, (gate * dbeta).sum(dim=0), dgate, dbeta, dwo, None
@@ -303,7 +303,7 @@ class CnfHidden(torch.autograd.Function):
             zs.append(z)
             hs.append(h)
             cur = h
-        zo = ops.conv1x1(_packed(wo, False), None, cur.view(1, R2, cur.shape[1])).view(R2, -1)
+        zo = ops.conv1x1_train(_packed(wo, False), None, cur.view(1, R2, cur.shape[1])).view(R2, -1)
         ctx.save_for_backward(xp, w1, b1, g1, be1, w2, b2, g2, be2, wo, zs[0], hs[0], zs[1], hs[1])
         ctx.n = n
         return zo[:, :wo.shape[0]]
@@ -341,7 +341,7 @@ class CnfHidden(torch.autograd.Function):
                        "caspr_conv1x1_cnf_act_bwd_bf16x6_f32")
         dw1 = torch.empty(c1, c0, device=dev, dtype=torch.float32)
         T.conv1x1_wgrad(dz1.view(1, R2, c1), xp.view(1, R2, c0), c0, c1, dw1, None)
-        dx = ops.conv1x1(_packed(w1, True), None, dz1.view(1, R2, c1)).view(R2, -1) if ctx.needs_input_grad[0] else None
+        dx = ops.conv1x1_train(_packed(w1, True), None, dz1.view(1, R2, c1)).view(R2, -1) if ctx.needs_input_grad[0] else None
         return (dx, dw1, (g1 * db1).sum(dim=0), dg1, db1, dw2, (g2 * db2).sum(dim=0), dg2, db2, dwo, None)
 
 
@@ -492,7 +492,7 @@ class LatentSolve(torch.autograd.Function):
         def f(z):
             a = [z.contiguous()]
             for i in range(4):
-                y = ops.conv1x1(pk[i], bd[i], a[-1].view(1, B, -1)).view(B, -1)[:, :ws[i].shape[0]]
+                y = ops.conv1x1_train(pk[i], bd[i], a[-1].view(1, B, -1)).view(B, -1)[:, :ws[i].shape[0]]
                 a.append(torch.tanh(y) if i < 3 else y)
             tape.append(a[:4])
             return a[4]
@@ -529,7 +529,7 @@ class LatentSolve(torch.autograd.Function):
                 d = g.contiguous() if i == 3 else torch.ops.aten.tanh_backward(g, a[i + 1])    # tanh' from the layer's stored output: one launch
                 deltas[i].append(d)
                 inputs[i].append(a[i])
-                g = ops.conv1x1(pkt[i], None, d.view(1, B, -1)).view(B, -1)[:, :ws[i].shape[1]]
+                g = ops.conv1x1_train(pkt[i], None, d.view(1, B, -1)).view(B, -1)[:, :ws[i].shape[1]]
             return g
         Tu = gout.shape[1]
         gz = gout[:, Tu - 1].clone()

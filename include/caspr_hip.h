@@ -257,6 +257,33 @@ int caspr_conv1x1_x6w_part_f32(const void *wpk_main, const void *wpk_tail, const
                                const float *in_scale, const float *in_shift, int in_relu, int in_relu_from, float *Y, int ldy, int B,
                                int P, int Cin, int Cout, int mt_begin, int mt_end, int with_tail, int reserve_cus, void *ws, long ws_bytes,
                                void *stream);
+
+/* ---- The same layers on THREE f16 products per f32 product (config.conv_split = "f16x3"; csrc/gemm_f16x3w.hip) ----------------------
+ * The 512-channel tiles of the three entries above on v_mfma_f32_32x32x16_f16: the activation (after the producer's GroupNorm / ReLU)
+ * is multiplied by 2^4, the layer's weights by the power of two that puts max |W| in [2^14, 2^15) -- found on the device by
+ * caspr_pack_weight_h3w (no host synchronisation; capturable) and stored behind the pack --, both are split into two f16 planes by
+ * round-to-nearest, w . x ~ w2 x1 + w1 x2 + w1 x1 with f32 accumulation, unscaled exactly at the read-out.  The < 512-channel
+ * remainder (wpk_tail) stays on the bf16x6 kernels.
+ *   wpk_main  caspr_pack_weight_h3w over the first Cout - Cout % 512 rows (caspr_h3w_packed_bytes(that, Cin) bytes);
+ *   status    one 32-bit word in device memory.  Range guard: an input value that is not below 65520 in magnitude after the 2^4 scale
+ *             (|x| >= 4095, a NaN or an infinity included) makes all 512 outputs of its row in the tile NaN and ORs 1 into *status;
+ *             rows without such a value keep their bits; the GroupNorm statistics of a batch entry with such a row are NaN.  The
+ *             entries never clear the word.  Remedy: conv_split = "bf16x6".                                                        */
+long caspr_h3w_packed_bytes(int Cout, int Cin);
+int caspr_pack_weight_h3w(const float *w, int ldw, int Cout, int col0, int ncols, void *packed, void *stream);
+int caspr_conv1x1_h3w_f32(const void *wpk_main, const void *wpk_tail, const float *bias, const float *bbias, const float *X, int ldx,
+                          const float *in_scale, const float *in_shift, int in_relu, int in_relu_from, float *Y, int ldy, int B,
+                          int P, int Cin, int Cout, int G, const float *gamma, const float *beta, float eps, float *scale,
+                          float *shift, float *pmax, float *mean, float *rstd, void *ws, long ws_bytes, unsigned *status, void *stream);
+int caspr_conv1x1_h3w_pooled_f32(const void *wpk_main, const void *wpk_tail, const float *bias, const float *bbias, const float *X, int ldx,
+                                 const float *in_scale, const float *in_shift, int in_relu, int in_relu_from, float *Y, int ldy, int B,
+                                 int P, int Cin, int Cout, int G, int pool, const float *gamma, const float *beta, float eps,
+                                 float *scale, float *shift, float *pmax, float *mean, float *rstd, void *ws, long ws_bytes, unsigned *status,
+                                 void *stream);
+int caspr_conv1x1_h3w_part_f32(const void *wpk_main, const void *wpk_tail, const float *bias, const float *bbias, const float *X, int ldx,
+                               const float *in_scale, const float *in_shift, int in_relu, int in_relu_from, float *Y, int ldy, int B,
+                               int P, int Cin, int Cout, int mt_begin, int mt_end, int with_tail, int reserve_cus, void *ws, long ws_bytes,
+                               unsigned *status, void *stream);
 int caspr_conv_gn_finalize_f32(const void *ws, long ws_bytes, int B, int P, int Cout, int G, int g_begin, int g_end, int pool,
                                const float *gamma, const float *beta, float eps, float *scale, float *shift, float *pmax, float *mean,
                                float *rstd, void *stream);
