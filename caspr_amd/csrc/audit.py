@@ -1,4 +1,4 @@
-"""Code-object audit of the kernels that manage the accumulator file by hand (ode_bf16x6w.hip, its f16x3 copy ode_f16x3w.hip, gemm_bf16x6w.hip, its f16x3 copy gemm_f16x3w.hip).
+"""Code-object audit of the kernels that manage the accumulator file by hand (ode_bf16x6w.hip, its f16x3 copy ode_f16x3w.hip, the adaptive solve on that copy ode_dp5_f16x3w.hip, gemm_bf16x6w.hip, its f16x3 copy gemm_f16x3w.hip).
 
 Both keep 256 live values at FIXED addresses a0..a255 across separate inline-asm statements.  A clobber list does not reserve
 registers between statements: what keeps hipcc out of the AGPRs is the hidden flag -amdgpu-mfma-vgpr-form (build.py EXTRA) plus the
@@ -116,6 +116,34 @@ def audit_cnf_h3w(obj):
             "cvt_pk": count(r"v_cvt_pk_f16_f32")}
 
 
+def audit_cnf_dp5_h3w(obj):
+    """cnf_dp5_h3w_kernel (ode_dp5_f16x3w.hip: the adaptive Dormand-Prince loop around the evaluation of the kernel above): the contract
+    of audit_cnf_h3w -- no scratch, agpr_count 256, exactly the accumulator moves the source writes (ONE copy of the stage body: 256
+    zeroing writes + 256 plane writes; 256 reads in pass 0, 256 plane reads in passes 1-3) and no v_accvgpr_mov, layer 1's MFMAs (8
+    pieces x 4 regions x 6) on a[..], every other MFMA in the VGPR form, all of them v_mfma_f32_32x32x16_f16, M0 touched by the LDS-DMA
+    statements only.  Also returned, not judged: cvt_pk, and vgpr_count, the metadata's `.vgpr_count` -- on gfx950 the COMBINED register count of a wave, the
+    VGPRs rounded up to the allocation granule of 8 plus the 256 accumulators (488 = 232 + 256 with the tested compiler, whose resource remark counts
+    229 VGPRs in use; cnf_rk4_h3w_kernel: 464 = 208 + 256)."""
+    notes, dis = _code_object(obj)
+    k = "_Z18cnf_dp5_h3w_kernel12CnfDp5H3Args"
+    meta, ins = _kernel(notes, dis, k)
+    count = lambda pat: sum(1 for i in ins if re.match(pat, i))
+    _no_spills(meta, ins, k)
+    _need(re.search(r"\.agpr_count:\s+256\b", meta), k + ": agpr_count != 256")
+    r, w = count(r"v_accvgpr_read_b32"), count(r"v_accvgpr_write_b32")
+    _need(r == 512 and w == 512 and count(r"v_accvgpr_mov") == 0, "%s: %d reads / %d writes of the accumulator file (512 / 512 in the source): the compiler touches it" % (k, r, w))
+    mfma = [i for i in ins if i.startswith("v_mfma")]
+    on_acc = [i for i in mfma if re.match(r"v_mfma_f32_32x32x16_f16 a\[", i)]
+    _need(len(on_acc) == 8 * 4 * 6 and all(" a[" not in i for i in mfma if i not in on_acc), "%s: %d of %d MFMAs on a[..] (192 expected, all others on VGPRs)" % (k, len(on_acc), len(mfma)))
+    _need(all(i.startswith("v_mfma_f32_32x32x16_f16") for i in mfma), "%s: an MFMA that is not v_mfma_f32_32x32x16_f16" % k)
+    dma = count(r"global_load_lds_dwordx4")
+    m0 = sum(1 for i in ins if re.search(r"\bm0\b", i))
+    _need(dma > 20 and m0 == dma, "%s: %d LDS-DMA instructions, %d M0 accesses" % (k, dma, m0))
+    vgpr = re.search(r"\.vgpr_count:\s+(\d+)", meta)
+    return {"kernel": k, "accvgpr_reads": r, "accvgpr_writes": w, "mfma": len(mfma), "mfma_on_acc": len(on_acc), "lds_dma": dma,
+            "cvt_pk": count(r"v_cvt_pk_f16_f32"), "vgpr_count": int(vgpr.group(1)) if vgpr else None}
+
+
 def audit_conv_x6w(obj):
     """conv1x1_x6w_kernel (all instantiations; persistent since round 4): no scratch, every MFMA on the hand-managed a[..] tiles, the
     accumulator file zeroed once in the prologue and read out + zeroed again in the two instances of the tile read-out (one per chunk
@@ -157,7 +185,7 @@ def audit_conv_h3w(obj):
     return out
 
 
-AUDITS = {"ode_bf16x6w.hip": audit_cnf_x6w, "ode_f16x3w.hip": audit_cnf_h3w, "gemm_bf16x6w.hip": audit_conv_x6w, "gemm_f16x3w.hip": audit_conv_h3w}
+AUDITS = {"ode_bf16x6w.hip": audit_cnf_x6w, "ode_f16x3w.hip": audit_cnf_h3w, "ode_dp5_f16x3w.hip": audit_cnf_dp5_h3w, "gemm_bf16x6w.hip": audit_conv_x6w, "gemm_f16x3w.hip": audit_conv_h3w}
 
 
 def audit_objects(objs_by_source):

@@ -6,7 +6,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.abspath(os.path.join(HERE, "..", "..")))
-SOURCES = ["point_ops.hip", "gemm.hip", "gemm_bf16x6.hip", "gemm_bf16x6w.hip", "gemm_f16x3w.hip", "sa_mlp.hip", "ode.hip", "ode_bf16x6.hip", "ode_bf16x6w.hip", "ode_f16x3w.hip", "cnf_frame_steps.hip", "ode_dp5.hip", "ode_train_fwd.hip", "ode_latent_dp5.hip", "backward.hip", "backward_points.hip", "backward_flow.hip", "emd.hip", "pose.hip", "base_sample.hip"]
+SOURCES = ["point_ops.hip", "gemm.hip", "gemm_bf16x6.hip", "gemm_bf16x6w.hip", "gemm_f16x3w.hip", "sa_mlp.hip", "ode.hip", "ode_bf16x6.hip", "ode_bf16x6w.hip", "ode_f16x3w.hip", "cnf_frame_steps.hip", "ode_dp5.hip", "ode_dp5_f16x3w.hip", "ode_train_fwd.hip", "ode_latent_dp5.hip", "backward.hip", "backward_points.hip", "backward_flow.hip", "emd.hip", "pose.hip", "base_sample.hip"]
 EXTRA = {"point_ops.hip": ["-ffp-contract=off"], "emd.hip": ["-ffp-contract=off"], "pose.hip": ["-ffp-contract=off"],
          "cnf_frame_steps.hip": ["-ffp-contract=off"],   # its f64 decisions are restated operation by operation (tests/frame_steps_ref.py)
          "base_sample.hip": ["-ffp-contract=off"],   # its log-density must round as ATen's separate kernels do (see the file's header)
@@ -18,6 +18,7 @@ EXTRA = {"point_ops.hip": ["-ffp-contract=off"], "emd.hip": ["-ffp-contract=off"
          # must take the VGPR form there, or it would park them in AGPRs it believes free (see the kernel's header)
          "ode_bf16x6w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
          "ode_f16x3w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],   # the same, on f16
+         "ode_dp5_f16x3w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],   # ... and its evaluation under the adaptive loop
          "gemm_bf16x6w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
          "gemm_f16x3w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"]}   # its f16x3 copy
 # CASPR_BUILD_DEBUG=1: the flavour with phase-trace hooks and experiment switches (-DCASPR_DEBUG_HOOKS, see common.h), built
@@ -85,7 +86,7 @@ def build(force=False, verbose=False):
                     raise
                 import warnings
                 warnings.warn("caspr_amd build: code-object audit FAILED and was skipped on request (CASPR_SKIP_AUDIT=1):\n%s\n"
-                              "run `pytest -m gpu` before trusting cnf_rk4_x6w_kernel / cnf_rk4_h3w_kernel / conv1x1_x6w_kernel / conv1x1_h3w_kernel" % e, RuntimeWarning)
+                              "run `pytest -m gpu` before trusting cnf_rk4_x6w_kernel / cnf_rk4_h3w_kernel / cnf_dp5_h3w_kernel / conv1x1_x6w_kernel / conv1x1_h3w_kernel" % e, RuntimeWarning)
         run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUT] + objs)
     return OUT
 

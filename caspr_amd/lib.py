@@ -111,6 +111,10 @@ SIGNATURES = {
     "caspr_cnf_dopri5_f32": (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_fp, ctypes.c_void_p, c_fp, ctypes.c_void_p, c_fp, c_fp, c_fp, c_int, c_float,
                                      c_float, c_float, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, ctypes.c_void_p, c_long,
                                      c_fp, c_ip, c_stream]),
+    "caspr_cnf_dopri5_h3_ws_bytes": (c_long, [c_int, c_int, c_int]),
+    "caspr_cnf_dopri5_h3_f32": (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_fp, ctypes.c_void_p, c_fp, ctypes.c_void_p, c_fp, c_fp, c_fp, c_int, c_float,
+                                        c_float, c_float, c_int, c_int, c_fp, c_fp, ctypes.c_void_p, c_fp, c_int, c_int, ctypes.c_void_p, c_long,
+                                        c_fp, c_ip, c_stream]),
     "caspr_chamfer_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_stream]),
     "caspr_emd_ws_bytes": (c_long, [c_int, c_int, c_int]),
     "caspr_emd_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp, ctypes.c_void_p, c_long, c_stream]),

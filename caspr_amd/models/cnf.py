@@ -8,7 +8,8 @@ trajectory does not depend on it.
 
 OPTION `method="dopri5"` (inference only): the reference's adaptive solve at `test_atol / test_rtol` on the
 GPU (ops.cnf_dopri5, csrc/ode_dp5.hip), error control per frame; `get_nfe()` then reports the measured
-maximum over frames.  RK4 stays the default and the training path.
+maximum over frames.  RK4 stays the default and the training path.  With ops.CNF_DP5_SPLIT = "f16x3" (opt-in) its
+sampling direction runs on the f16x3 evaluation (csrc/ode_dp5_f16x3w.hip).
 """
 import torch
 import torch.nn as nn
@@ -44,6 +45,7 @@ class CNF(nn.Module):
         self.method = method          # "dopri5": integrate() solves to test_atol / test_rtol (inference only)
         self.max_attempts = max_attempts
         self.last_nfe_per_frame = None   # dopri5: (BT,) int32 device tensor of the last counted solve
+        self.last_dp5_kernel = None      # dopri5: the kernel that ran it (ops.cnf_dopri5's trace item "kernel" when the f16 packs were handed over)
         self._count_evals = True      # False while the accuracy guard repeats a solve (CaSPR._guard_cnf): get_nfe() counts the real one only
         self._narrow = False          # True while the guard runs its check solve: the 64-point sampling kernel (ops.cnf_rk4(narrow=True))
         # Per-frame step counts of the SAMPLING direction (CaSPR(cnf_steps="frame"); ops.cnf_frame_steps chooses them): when frame_steps
@@ -139,12 +141,16 @@ class CNF(nn.Module):
                 raise ValueError("CNF(method='dopri5') cannot run under stream capture: the host loop reads the device after every attempt")
             if w1x is None:
                 raise ValueError("CNF(method='dopri5') needs the bf16x6 kernel (ops.CNF_BF16X6, 512-512-512)")
+            # ops.CNF_DP5_SPLIT = "f16x3" (opt-in): the sampling direction on the f16x3 evaluation (ops.cnf_dopri5 routes: n >= 128)
+            w1h, w2h = self._weights_h3() if (ops.cnf_dp5_split() == "f16x3" and logpx is None and ops.CNF_BF16X6) else (None, None)
             res = ops.cnf_dopri5(x.contiguous(), hyper, w["tcol"], w["w0"], w["b0"], w["b1"], w["b2"], w["w3"], w["b3"], w1x, w2x,
                                  self.end_time(), self.test_rtol, self.test_atol, reverse, mbn_in, mbn_out, e=e,
-                                 logp=None if logpx is None else logpx.contiguous(), max_attempts=self.max_attempts, return_trace=True)
+                                 logp=None if logpx is None else logpx.contiguous(), max_attempts=self.max_attempts, return_trace=True,
+                                 w1h=w1h, w2h=w2h)
             info, res = res[-1], (res[0] if logpx is None else res[:-1])
             if self._count_evals:
                 self.last_nfe_per_frame = info["nfe"]
+                self.last_dp5_kernel = info.get("kernel", "cnf_dp5_kernel<%s>" % ("false" if logpx is None else "true"))
                 self.odefunc._num_evals += info["nfe"].max().to(self.odefunc._num_evals.dtype)
             return res
         # the f16x3 split: plain sampling solves only (ops.cnf_rk4 routes).  The guard's check solve (_count_evals is False then) stays on

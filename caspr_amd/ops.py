@@ -259,7 +259,8 @@ CONV_X6W = _cfg.conv_x6w             # ... and the layers with >= 512 output cha
 CNF_BF16X6 = _mode == "bf16x6"       # point-CNF solves on the bf16x6 kernel
 CNF_SPLIT = _cfg.cnf_split           # "f16x3": the sampling solve (no divergence, n >= 128) on three f16 products per f32 product (csrc/ode_f16x3w.hip);
                                      # matmul_mode()["cnf"] says "bf16x6" for both (the family; bench.py keys its roofline block on that string)
-
+CNF_DP5_SPLIT = _cfg.cnf_dp5_split   # "f16x3": the ADAPTIVE solve's sampling direction (cnf_method="dopri5", no divergence, n >= 128) on csrc/ode_dp5_f16x3w.hip;
+                                     # "bf16x6" (the default): csrc/ode_dp5.hip on every call.  Independent of CNF_SPLIT, whose default is "f16x3"
 
 CONV_SPLIT = _cfg.conv_split         # "f16x3": the layers of the persistent 512-channel conv on three f16 products per f32 product (csrc/gemm_f16x3w.hip),
                                      # inference only; matmul_mode()["conv"] says "bf16x6" for both (the family), the timer keys stay what they are
@@ -270,6 +271,13 @@ def conv_split():
     if CONV_SPLIT not in ("bf16x6", "f16x3"):
         raise ValueError("caspr_amd.ops.CONV_SPLIT must be 'bf16x6' or 'f16x3', got %r" % (CONV_SPLIT,))
     return CONV_SPLIT
+
+
+def cnf_dp5_split():
+    """CNF_DP5_SPLIT, validated where it is read (a run-time switch: a misspelt value must not select bf16x6 silently)."""
+    if CNF_DP5_SPLIT not in ("bf16x6", "f16x3"):
+        raise ValueError("caspr_amd.ops.CNF_DP5_SPLIT must be 'bf16x6' or 'f16x3', got %r" % (CNF_DP5_SPLIT,))
+    return CNF_DP5_SPLIT
 
 
 def cnf_split():
@@ -1192,7 +1200,7 @@ _h3_word = {}            # stream key -> the device word (zeroed by the C entry 
 
 def _h3_raise_if_failed(key, wait=False):
     ring = _h3_status.get(key)
-    failed = False
+    bits = 0                                         # bit 0: cnf_rk4_h3w_kernel, bit 1: cnf_dp5_h3w_kernel (include/caspr_hip.h)
     while ring:
         host, ev = ring[0]
         if wait:
@@ -1200,13 +1208,20 @@ def _h3_raise_if_failed(key, wait=False):
         if not ev.query():
             break
         ring.pop(0)
-        failed = failed or int(host[0]) != 0
+        bits |= int(host[0])
         _h3_pool.append(host)
-    if failed:
-        raise _lib.CasprHipError("caspr_cnf_rk4_h3_f32: the range guard of the f16x3 point-CNF solve tripped: a hidden activation of the ODE "
-                                 "function reached 4095, which is not finite in f16 after the kernel's 2^4 prescale; the samples of the affected "
-                                 "points were set to NaN.  Remedy: cnf_split=\"bf16x6\" (caspr_amd.config.config.cnf_split / caspr_amd.ops.CNF_SPLIT), "
-                                 "the six-product bf16 kernel, which has f32's exponent range")
+    if bits:
+        # one error for everything that has arrived: each kernel whose guard tripped is named with its own remedy
+        what = []
+        if bits & 1:
+            what.append("caspr_cnf_rk4_h3_f32 (the fixed-step sampling solve): the samples of the affected points were set to NaN.  Remedy: "
+                        "cnf_split=\"bf16x6\" (caspr_amd.config.config.cnf_split / caspr_amd.ops.CNF_SPLIT)")
+        if bits & 2:
+            what.append("caspr_cnf_dopri5_h3_f32 (the adaptive solve): the affected FRAMES were retired with NaN in all of their samples.  Remedy: "
+                        "cnf_dp5_split=\"bf16x6\" (caspr_amd.config.config.cnf_dp5_split / caspr_amd.ops.CNF_DP5_SPLIT)")
+        raise _lib.CasprHipError("the range guard of the f16x3 point-CNF solve tripped: a hidden activation of the ODE function reached 4095, which is "
+                                 "not finite in f16 after the kernel's 2^4 prescale.  " + ";  ".join(what) + ": the six-product bf16 kernel, which has "
+                                 "f32's exponent range")
 
 
 def _h3_track(key, word):
@@ -1437,11 +1452,16 @@ DP5_TRACE_HEAD, DP5_TRACE_ROW = 8, 5      # include/caspr_hip.h: the trace layou
 
 
 def cnf_dopri5(y, hyper, tcol, w0, b0, b1, b2, w3, b3, w1x, w2x, t_end, rtol, atol, reverse, mbn_in=None, mbn_out=None,
-               e=None, logp=None, max_attempts=1000, return_trace=False):
+               e=None, logp=None, max_attempts=1000, return_trace=False, w1h=None, w2h=None):
     """Adaptive Dormand-Prince 5(4) solve of one CNF block to a tolerance (cnf.py:96-118: what the reference runs on every call), error
     control PER FRAME (csrc/ode_dp5.hip).  Arguments as cnf_rk4 with the bf16x6 packs w1x / w2x (pack_cnf_x6) required.  Returns x or
     (x, logp); with return_trace a dict is appended: "d0", "d1", "d2", "h0", "dt0" (BT,), "attempts" (BT, max_attempts, 5) rows
     [t, dt, ratio x, ratio logp, accepted], "accepted", "rejected", "nfe" (BT,) int32 -- all on the device.
+    w1h / w2h (pack_cnf_h3): when both are given and the call is a plain sampling solve (e is None, n >= 128), the f16x3 kernel runs it
+    (csrc/ode_dp5_f16x3w.hip, three f16 products per f32 product); every other call goes where it goes without them.  Its range guard
+    retires a frame with NaN in all of its rows and reports through check_deferred_errors.  A call that hands the packs over gets two
+    more items in its trace dict, whichever kernel ran: "kernel", the kernel's name (a str, the only item that is not a tensor), and
+    "finished" (BT,) int32 (1: reached t_end; 3: retired by the range guard).  Without the packs the dict is what it always was.
     The host reads one device word per attempt: not usable under stream capture or with autograd (training keeps RK4).
     Raises CasprHipError when a frame has not reached t_end after max_attempts attempts."""
     _chk_f32(y, hyper, tcol, w0, b0, b1, b2, w3, b3, mbn_in, mbn_out, e, logp)
@@ -1475,17 +1495,39 @@ def cnf_dopri5(y, hyper, tcol, w0, b0, b1, b2, w3, b3, w1x, w2x, t_end, rtol, at
     trace = torch.empty(BT, DP5_TRACE_HEAD + DP5_TRACE_ROW * max_attempts, device=y.device, dtype=torch.float32)
     counters = torch.empty(BT, 4, device=y.device, dtype=torch.int32)
     L = _lib.load()
-    ws = _workspace(L.caspr_cnf_dopri5_ws_bytes(BT, n, max_attempts), y.device)
-    with timed("cnf_dopri5"):
-        _lib.check(L.caspr_cnf_dopri5_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1x), _p(b1), _p(w2x), _p(b2), _p(w3), _p(b3),
-                                          w0.shape[0], float(t_end), rtol, atol, max_attempts, int(bool(reverse)), _p(mbn_in), _p(mbn_out),
-                                          _p(e), _p(logp), _p(lp_out), _p(out), BT, n, _p(ws), ws.numel(), _p(trace), _p(counters), _stream()),
-                   "caspr_cnf_dopri5_f32")
+    h3 = w1h is not None and w2h is not None and e is None and n >= 128
+    if h3:
+        nbytes = L.caspr_cnf_h3_packed_bytes()
+        if w1h.numel() != nbytes or w2h.numel() != nbytes or w1h.dtype != torch.uint8 or w2h.dtype != torch.uint8:
+            raise ValueError("cnf_dopri5: w1h / w2h must be the packs of pack_cnf_h3")
+        key = (y.device.index, torch.cuda.current_stream().cuda_stream)
+        _h3_raise_if_failed(key)                         # status of the previous solves on this stream, if it has arrived
+        word = _h3_word.get(key)
+        if word is None:
+            word = _h3_word[key] = torch.zeros(1, device=y.device, dtype=torch.int32)
+        ws = _workspace(L.caspr_cnf_dopri5_h3_ws_bytes(BT, n, max_attempts), y.device)
+        with timed("cnf_dopri5"):
+            _lib.check(L.caspr_cnf_dopri5_h3_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1h), _p(b1), _p(w2h), _p(b2), _p(w3),
+                                                 _p(b3), w0.shape[0], float(t_end), rtol, atol, max_attempts, int(bool(reverse)), _p(mbn_in),
+                                                 _p(mbn_out), _p(word), _p(out), BT, n, _p(ws), ws.numel(), _p(trace), _p(counters), _stream()),
+                       "caspr_cnf_dopri5_h3_f32")
+        _h3_track(key, word)
+    else:
+        ws = _workspace(L.caspr_cnf_dopri5_ws_bytes(BT, n, max_attempts), y.device)
+        with timed("cnf_dopri5"):
+            _lib.check(L.caspr_cnf_dopri5_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1x), _p(b1), _p(w2x), _p(b2), _p(w3), _p(b3),
+                                              w0.shape[0], float(t_end), rtol, atol, max_attempts, int(bool(reverse)), _p(mbn_in), _p(mbn_out),
+                                              _p(e), _p(logp), _p(lp_out), _p(out), BT, n, _p(ws), ws.numel(), _p(trace), _p(counters), _stream()),
+                       "caspr_cnf_dopri5_f32")
     res = (out,) if e is None else (out, lp_out)
     if return_trace:
-        res = res + ({"d0": trace[:, 0], "d1": trace[:, 1], "d2": trace[:, 2], "h0": trace[:, 3], "dt0": trace[:, 4],
-                      "attempts": trace[:, DP5_TRACE_HEAD:].view(BT, max_attempts, DP5_TRACE_ROW),
-                      "accepted": counters[:, 0], "rejected": counters[:, 1], "nfe": counters[:, 2]},)
+        info = {"d0": trace[:, 0], "d1": trace[:, 1], "d2": trace[:, 2], "h0": trace[:, 3], "dt0": trace[:, 4],
+                "attempts": trace[:, DP5_TRACE_HEAD:].view(BT, max_attempts, DP5_TRACE_ROW),
+                "accepted": counters[:, 0], "rejected": counters[:, 1], "nfe": counters[:, 2]}
+        if w1h is not None and w2h is not None:
+            info["finished"] = counters[:, 3]
+            info["kernel"] = "cnf_dp5_h3w_kernel" if h3 else "cnf_dp5_kernel<%s>" % ("true" if e is not None else "false")
+        res = res + (info,)
     return res[0] if len(res) == 1 else res
 
 

@@ -460,6 +460,28 @@ int caspr_cnf_dopri5_f32(const float *y_in, const float *hyper, int ldh, const f
                          float *logp_out, float *y_out, int BT, int n, void *ws, long ws_bytes,
                          float *trace, int32_t *counters, void *stream);
 
+/* The same adaptive solve in the SAMPLING direction (models/cnf.py:96-118 with logpx = None; flow.py:96-99) on the f16x3 evaluation
+ * of caspr_cnf_rk4_h3_f32 (csrc/ode_dp5_f16x3w.hip; the Python host's config.cnf_dp5_split = "f16x3"): 128 points per workgroup, three
+ * f16 products per f32 product, the state is x only.  Launch protocol, controller, per-frame norms, trace and counter layout as
+ * caspr_cnf_dopri5_f32 (the trace's "ratio logp" column is 0).  Arguments as caspr_cnf_dopri5_f32 without e / logp_in / logp_out, with
+ *   w1h / w2h  the packs of caspr_pack_weight_cnf_h3 in place of the bf16x6 packs;
+ *   status     one device word, zeroed by the entry on `stream` in front of the first launch.  RANGE GUARD: a point one of whose
+ *              hidden activations is not finite in f16 after the 2^4 scale (|x| >= 4095) would poison its frame's error norm.  Bit 1
+ *              of the word is set (value 2; caspr_cnf_rk4_h3_f32 sets bit 0), and at the next launch the FRAME retires: NaN in all of
+ *              its output rows, counters[f][3] = 3 (finished | guard), the attempt that was running traced as rejected with a NaN
+ *              ratio.  It never runs on to max_attempts, the call's return code is unaffected, the other frames keep their bits.  The
+ *              remedy is caspr_cnf_dopri5_f32.
+ *   ws         >= caspr_cnf_dopri5_h3_ws_bytes(BT, n, max_attempts) bytes, 256-byte aligned.
+ * Synchronises the stream like caspr_cnf_dopri5_f32; CASPR_ENOCONV / CASPR_EUNSUP as there.                                  */
+long caspr_cnf_dopri5_h3_ws_bytes(int BT, int n, int max_attempts);
+int caspr_cnf_dopri5_h3_f32(const float *y_in, const float *hyper, int ldh, const float *tcol,
+                            const float *w0, const float *b0, const void *w1h, const float *b1,
+                            const void *w2h, const float *b2, const float *w3, const float *b3, int H,
+                            float t_end, float rtol, float atol, int max_attempts, int reverse,
+                            const float *mbn_in, const float *mbn_out, unsigned *status, float *y_out,
+                            int BT, int n, void *ws, long ws_bytes, float *trace, int32_t *counters,
+                            void *stream);
+
 /* ---------------- Chamfer (tk3dv.extern.chamfer.ChamferDistance): utils/evaluations.py:40 --------
  * p (B,n,3), q (B,m,3) -> dist1 (B,n) = min_j |p_i-q_j|^2 , dist2 (B,m).                            */
 int caspr_chamfer_f32(const float *p, const float *q, int B, int n, int m, float *dist1, float *dist2,
