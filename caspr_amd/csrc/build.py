@@ -6,7 +6,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.abspath(os.path.join(HERE, "..", "..")))
-SOURCES = ["point_ops.hip", "gemm.hip", "gemm_bf16x6.hip", "gemm_bf16x6w.hip", "gemm_f16x3w.hip", "sa_mlp.hip", "ode.hip", "ode_bf16x6.hip", "ode_bf16x6w.hip", "ode_f16x3w.hip", "cnf_frame_steps.hip", "ode_dp5.hip", "ode_dp5_f16x3w.hip", "ode_train_fwd.hip", "ode_latent_dp5.hip", "backward.hip", "backward_points.hip", "backward_flow.hip", "emd.hip", "pose.hip", "base_sample.hip"]
+SOURCES = ["point_ops.hip", "gemm.hip", "gemm_bf16x6.hip", "gemm_bf16x6w.hip", "gemm_f16x3w.hip", "sa_mlp.hip", "ode.hip", "ode_bf16x6.hip", "ode_bf16x6w.hip", "ode_f16x3w.hip", "cnf_frame_steps.hip", "ode_dp5.hip", "ode_dp5_f16x3w.hip", "ode_train_fwd.hip", "ode_sample_tape.hip", "ode_latent_dp5.hip", "backward.hip", "backward_points.hip", "backward_flow.hip", "backward_flow_value.hip", "emd.hip", "pose.hip", "base_sample.hip"]
 EXTRA = {"point_ops.hip": ["-ffp-contract=off"], "emd.hip": ["-ffp-contract=off"], "pose.hip": ["-ffp-contract=off"],
          "cnf_frame_steps.hip": ["-ffp-contract=off"],   # its f64 decisions are restated operation by operation (tests/frame_steps_ref.py)
          "base_sample.hip": ["-ffp-contract=off"],   # its log-density must round as ATen's separate kernels do (see the file's header)
@@ -14,6 +14,7 @@ EXTRA = {"point_ops.hip": ["-ffp-contract=off"], "emd.hip": ["-ffp-contract=off"
          "ode_bf16x6.hip": ["-mllvm", "-pragma-unroll-threshold=400000"],
          "ode_dp5.hip": ["-mllvm", "-pragma-unroll-threshold=400000"],   # the same evaluation body
          "ode_train_fwd.hip": ["-mllvm", "-pragma-unroll-threshold=400000"],   # ... and again (training forward of a CNF block)
+         "ode_sample_tape.hip": ["-mllvm", "-pragma-unroll-threshold=400000"],   # ... and the sampling solve that writes a tape
          # the 128-point CNF kernel keeps its layer-1 accumulators in the accumulator file BY HAND (inline asm): hipcc's own MFMAs
          # must take the VGPR form there, or it would park them in AGPRs it believes free (see the kernel's header)
          "ode_bf16x6w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],

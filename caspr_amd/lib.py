@@ -158,6 +158,16 @@ SIGNATURES = {
     "caspr_cnf_in_bwd_f32": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_long, c_int, c_int, c_long, c_fp, c_fp, c_fp, c_fp, c_stream]),
     "caspr_cnf_train_fwd_f32": (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_fp, ctypes.c_void_p, c_fp, ctypes.c_void_p, c_fp, c_fp, c_fp, c_int, c_fp, c_int,
                                         c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_stream]),
+    "caspr_cnf_sample_tape_f32": (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_fp, ctypes.c_void_p, c_fp, ctypes.c_void_p, c_fp, c_fp, c_fp, c_int, c_fp, c_int,
+                                          c_fp, c_fp, c_fp, c_int, c_int, c_stream]),
+    "caspr_cnf_value_splits": (c_int, [c_int]),
+    "caspr_cnf_in_value_f32": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_long, c_int, c_int, c_fp, c_int, c_stream]),
+    "caspr_cnf_in_value_bwd_f32": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_long, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_stream]),
+    "caspr_cnf_act_value_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_long, c_int, c_int, c_fp, c_int, c_stream]),
+    "caspr_cnf_act_value_bwd_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_long, c_int, c_int, c_fp, c_int, c_fp, c_fp, c_stream]),
+    "caspr_cnf_act_value_bwd_out_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_fp, c_int, c_long, c_int, c_int, c_fp, c_int, c_fp, c_fp, c_stream]),
+    "caspr_cnf_out_value_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_int, c_long, c_int, c_fp, c_stream]),
+    "caspr_cnf_out_value_bwd_f32": (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_int, c_long, c_int, c_fp, c_fp, c_fp, c_stream]),
     "caspr_gn_rows_bwd_ws_bytes": (c_long, [c_int]),
     "caspr_gn_rows_bwd_f32": (c_int, [c_fp, c_int, c_long, c_int, c_int, c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_int, c_fp, c_int, c_ip,
                                       c_fp, c_int, c_fp, c_fp, c_int, ctypes.c_void_p, c_long, c_stream]),

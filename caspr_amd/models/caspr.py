@@ -609,10 +609,32 @@ class CaSPR(nn.Module):
             y = y.view((B, 1, num_points, input_dim)).expand((B, T, num_points, input_dim)).reshape((B * T, num_points, input_dim))
         return y.contiguous(), logp_y
 
-    def decode(self, z, num_points=1024, constant_in_time=False, truncate_std=None, sample_contours=None, y=None, _early=None, frame_ids=None):
+    def _check_differentiable(self, what):
+        """decode(differentiable=True) / reconstruct(differentiable=True): the options the gradient route does not cover, refused with
+        the reason (train/flow_grad.py: point_cnf_sample_train states the rest -- GPU tensors, the 512-wide ODE function, ops.CNF_BF16X6)."""
+        from .cnf import CNF
+        if not torch.is_grad_enabled():
+            raise ValueError("%s(differentiable=True) records a gradient, but grad mode is off (torch.no_grad()): drop the keyword for inference" % what)
+        if self.cnf_steps == "frame":
+            raise ValueError("%s(differentiable=True) differentiates the uniform RK4 solve: no gradient through per-frame step counts "
+                             "(cnf_steps=\"frame\" is an inference option)" % what)
+        if any(isinstance(l, CNF) and l.method != "rk4" for l in self.point_cnf.chain):
+            raise ValueError("%s(differentiable=True) differentiates the RK4 solve: no gradient through the adaptive solve "
+                             "(cnf_method=\"dopri5\" is an inference option)" % what)
+
+    def decode(self, z, num_points=1024, constant_in_time=False, truncate_std=None, sample_contours=None, y=None, _early=None, frame_ids=None,
+               differentiable=False):
         """caspr.py:204-267.  `y` (B,T,num_points,3) optionally supplies the base samples.
         frame_ids (device sampler only; ignored with the host sampler or a given `y`): the global ids the draw is keyed by, int64,
-        B*T of them (sequence * T + t) or, with constant_in_time, B (see _base_frame_ids); default: this batch is sequences 0 .. B-1."""
+        B*T of them (sequence * T + t) or, with constant_in_time, B (see _base_frame_ids); default: this batch is sequences 0 .. B-1.
+        differentiable: False (default) runs the inference kernels whatever the grad mode -- under grad mode the returned `x` is DETACHED
+        from the graph (no grad_fn; the accuracy guard is skipped there).  True: `x` is differentiable in z, in a given `y` and in every
+        parameter of the point CNF, as the reference's decode is (caspr.py:262 through torchdiffeq): the sampling solve runs as one
+        autograd node per block with a tape of (BT,n,3) tensors (train/flow_grad.py: point_cnf_sample_train; discretise-then-optimise:
+        the gradient of the RK4 map itself).  Needs grad mode, GPU tensors, uniform RK4 steps (not cnf_method="dopri5", not
+        cnf_steps="frame"): otherwise a ValueError says which; no guard on this route."""
+        if differentiable:
+            self._check_differentiable("decode")
         B, T, H = z.size()
         input_dim = self.cnf_args.input_dim
         given = y is not None
@@ -625,7 +647,10 @@ class CaSPR(nn.Module):
         else:
             logp_y = standard_normal_logprob(y).view(B * T, num_points, -1).sum(2)
         z = z.reshape((B * T, H))
-        if self.cnf_steps == "frame" and y.is_cuda:
+        if differentiable:
+            from ..train.flow_grad import point_cnf_sample_train
+            x = point_cnf_sample_train(self.point_cnf, y, z)
+        elif self.cnf_steps == "frame" and y.is_cuda:
             x = self._decode_frame_steps(y, z)
         else:
             guard = self._guard_cnf_begin(y, z) if (self.check_tol is not None and y.is_cuda and not torch.is_grad_enabled()) else None
@@ -634,9 +659,22 @@ class CaSPR(nn.Module):
                 self._guard_cnf_end(guard, x)
         return y.view((B, T, num_points, input_dim)), logp_y.view((B, T, num_points)), x.view((B, T, num_points, input_dim))
 
+    @staticmethod
+    def _sequence_frame_ids(sequence_ids, B, T, constant_in_time, device):
+        """reconstruct()'s sequence_ids (B,) -> the frame ids decode() keys the device draw by (_base_frame_ids)."""
+        seq = torch.as_tensor(sequence_ids).to(device=device, dtype=torch.int64).reshape(-1)
+        if seq.numel() != B:
+            raise ValueError("sequence_ids must hold B = %d ids, got %d" % (B, seq.numel()))
+        if constant_in_time:
+            return seq | (1 << 62)
+        return (seq.view(B, 1) * T + torch.arange(T, device=device, dtype=torch.int64).view(1, T)).reshape(-1)
+
     def reconstruct(self, x, num_points=1024, constant_in_time=False, timestamps=None, max_timestamp=5.0,
-                    truncate_std=None, sample_contours=None, y=None, check_tol=_UNSET, sequence_ids=None):
+                    truncate_std=None, sample_contours=None, y=None, check_tol=_UNSET, sequence_ids=None, differentiable=False):
         """caspr.py:269-308 -> (y, logp_y, x, tnocs_pred).  `y` (B,T,num_points,3) optionally supplies the base samples.
+        differentiable=True: the plain serial composition the reference has -- encode -> aggregate_and_solve_latent ->
+        decode(differentiable=True) -- on the current stream, recorded by autograd (encoder, latent ODE and point CNF each through their
+        training route); no side streams, no early latent solve, no accuracy guard.  Same return tuple; see decode() for what it needs.
         check_tol: the accuracy guard's tolerance for THIS call (default: the model's `check_tol` attribute; None = off).
         sequence_ids (device sampler only; ignored with the host sampler or a given `y`): int64 (B,), the global index of each
         sequence (default arange(B)); a shard that passes its sequences' global indices draws what the unsharded batch draws.
@@ -645,9 +683,20 @@ class CaSPR(nn.Module):
             prev, self.check_tol = self.check_tol, check_tol
             try:
                 return self.reconstruct(x, num_points, constant_in_time, timestamps, max_timestamp, truncate_std, sample_contours, y,
-                                        sequence_ids=sequence_ids)
+                                        sequence_ids=sequence_ids, differentiable=differentiable)
             finally:
                 self.check_tol = prev
+        if differentiable:
+            self._check_differentiable("reconstruct")
+            B, T, N, _ = x.size()
+            all_times = x[:, :, 0, 3] / max_timestamp if timestamps is None else timestamps.view((1, -1)).repeat((B, 1)).to(x)
+            z0, tnocs_pred = self.encode(x)
+            frame_ids = None
+            if self.base_sampler == "device" and y is None and sequence_ids is not None:
+                frame_ids = self._sequence_frame_ids(sequence_ids, B, T, constant_in_time, x.device)
+            z = self.aggregate_and_solve_latent(z0, all_times)
+            y, logp_y, x = self.decode(z, num_points, constant_in_time, truncate_std, sample_contours, y=y, frame_ids=frame_ids, differentiable=True)
+            return y, logp_y, x, tnocs_pred
         with torch.no_grad():
             B, T, N, _ = x.size()
             if timestamps is None:
@@ -684,13 +733,7 @@ class CaSPR(nn.Module):
                 early = self._draw_early(B, T, num_points, constant_in_time, x.device)
             frame_ids = None
             if self.base_sampler == "device" and y is None and sequence_ids is not None:
-                seq = torch.as_tensor(sequence_ids).to(device=x.device, dtype=torch.int64).reshape(-1)
-                if seq.numel() != B:
-                    raise ValueError("sequence_ids must hold B = %d ids, got %d" % (B, seq.numel()))
-                if constant_in_time:
-                    frame_ids = seq | (1 << 62)
-                else:
-                    frame_ids = (seq.view(B, 1) * T + torch.arange(T, device=x.device, dtype=torch.int64).view(1, T)).reshape(-1)
+                frame_ids = self._sequence_frame_ids(sequence_ids, B, T, constant_in_time, x.device)
             with ops.timed("latent"):
                 z = self.aggregate_and_solve_latent(z0, all_times, plan, early_lat)
             self._early_latent_used = bool(early_lat is not None and early_lat.event is not None)     # for tests / tools

@@ -14,6 +14,9 @@ fused kernels caspr_cnf_act_f32 / caspr_cnf_act_bwd_f32 (`CnfAct`).  torch.autog
 around them: the (frames, C) gates, the (BT,n,3) RK4 combinations and the 3-channel output layer.  Fusing the
 activation into the GEMM epilogue and recomputing instead of storing the layer products is the next step
 (DESIGN.md section 7).  No CPU path: everything below requires GPU tensors.
+
+The SAMPLING direction of the point CNF (decode(differentiable=True); cnf.py:70-128 with reverse = True, caspr.py:262) is at the end of the
+file: CnfSampleSolve / point_cnf_sample_train, one node per block on value rows only.
 """
 import torch
 import torch.nn as nn
@@ -628,6 +631,36 @@ def _cnf_eval_fused(wb, t, y, G_lm, Bb_lm, tg_lm, tb_lm, e_rows, BT, n, widths):
     return CnfOut.apply(z, b3, parts[3], parts[7], e_rows, n, 32)
 
 
+def _hyper_layer_major(block, context):
+    """The four hyper networks of a CNF block for every frame, as both block nodes (CnfBlockSolve, CnfSampleSolve) and the taped route
+    take them: the context columns once per solve through `linear_rows` (constant over the solve; this is where dL/d context and the
+    hyper networks' gradients flow), the time column per evaluation.  All four layers' gate / bias rows live in layer-major 1-D tensors
+    ([layer][frame][channel]) so that the per-evaluation time update is one element-wise launch for all layers and the per-layer
+    (BT, C_l) tensors are contiguous views.  context (BT, zdim) -> G_lm, Bb_lm, tg_lm, tb_lm, widths."""
+    BT = context.shape[0]
+    c = context.contiguous()
+    G, Bb, tg, tb, widths = [], [], [], [], []
+    for l in block.odefunc.diffeq.layers:
+        wg, wb = l._hyper_gate.weight, l._hyper_bias.weight
+        G.append(linear_rows(c, wg[:, 1:].contiguous(), l._hyper_gate.bias))
+        Bb.append(linear_rows(c, wb[:, 1:].contiguous(), None))
+        tg.append(wg[:, 0])
+        tb.append(wb[:, 0])
+        widths.append(wg.shape[0])
+    G_lm, Bb_lm = torch.cat([g.reshape(-1) for g in G]), torch.cat([b_.reshape(-1) for b_ in Bb])
+    tg_lm = torch.cat([v.unsqueeze(0).expand(BT, -1).reshape(-1) for v in tg])
+    tb_lm = torch.cat([v.unsqueeze(0).expand(BT, -1).reshape(-1) for v in tb])
+    return G_lm, Bb_lm, tg_lm, tb_lm, tuple(widths)
+
+
+def _hyper_for_kernel(G_lm, Bb_lm, tg_lm, tb_lm, BT, widths):
+    """The layer-major hyper tensors in the form the solve kernels read (ops.cnf_rk4): hyper (BT, [gate l0..l3 | bias l0..l3]) and
+    tcol, one row of the time columns in the same order.  Detached: the kernels are not differentiated through."""
+    hyper = torch.cat(_layer_views(G_lm.detach(), BT, widths) + _layer_views(Bb_lm.detach(), BT, widths), dim=1).contiguous()
+    tcol = torch.cat([v[0] for v in _layer_views(tg_lm.detach(), BT, widths) + _layer_views(tb_lm.detach(), BT, widths)]).contiguous()
+    return hyper, tcol
+
+
 class CnfBlockSolve(torch.autograd.Function):
     """A CNF block's whole RK4 solve (forward direction, Hutchinson divergence for a given e) as ONE autograd node whose tape does not
     grow with the layer width: forward = one launch of caspr_cnf_train_fwd_f32, which keeps every layer product on chip and writes only
@@ -644,8 +677,7 @@ class CnfBlockSolve(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, logpx, G_lm, Bb_lm, tg_lm, tb_lm, t_end, e, w1x, w2x, steps, widths, *wb):
         BT, n, _ = x.shape
-        hyper = torch.cat(_layer_views(G_lm.detach(), BT, widths) + _layer_views(Bb_lm.detach(), BT, widths), dim=1).contiguous()
-        tcol = torch.cat([v[0] for v in _layer_views(tg_lm.detach(), BT, widths) + _layer_views(tb_lm.detach(), BT, widths)]).contiguous()
+        hyper, tcol = _hyper_for_kernel(G_lm, Bb_lm, tg_lm, tb_lm, BT, widths)
         w0, b0, w1, b1, w2, b2, w3, b3 = [t_.detach().contiguous() for t_ in wb]
         ec = e.detach().contiguous()
         y, lp, ys, ka, knd = T.cnf_train_fwd(x.detach().contiguous(), logpx.detach().contiguous(), ec, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3,
@@ -707,23 +739,8 @@ def cnf_block_train(block, x, context, logpx, e):
     t: 0 -> sqrt_end_time^2 with `block.rk4_steps` RK4 steps.  -> (x_T, logp_T), differentiable in every parameter."""
     layers = block.odefunc.diffeq.layers
     BT, n, _ = x.shape
-    c = context.contiguous()
-    # hyper networks: the context columns once per step (constant over the solve), the time column per evaluation.
-    # All four layers' gate / bias rows live in ONE (BT, sum C) tensor so that the per-evaluation time update is a
-    # handful of element-wise launches instead of five per layer.
-    G, Bb, tg, tb, widths = [], [], [], [], []
-    for l in layers:
-        wg, wb = l._hyper_gate.weight, l._hyper_bias.weight
-        G.append(linear_rows(c, wg[:, 1:].contiguous(), l._hyper_gate.bias))
-        Bb.append(linear_rows(c, wb[:, 1:].contiguous(), None))
-        tg.append(wg[:, 0])
-        tb.append(wb[:, 0])
-        widths.append(wg.shape[0])
-    # layer-major 1-D tensors ([layer][frame][channel]): one element-wise update per evaluation for all layers, per-layer contiguous views
-    G_lm, Bb_lm = torch.cat([g.reshape(-1) for g in G]), torch.cat([b_.reshape(-1) for b_ in Bb])
-    tg_lm = torch.cat([v.unsqueeze(0).expand(BT, -1).reshape(-1) for v in tg])
-    tb_lm = torch.cat([v.unsqueeze(0).expand(BT, -1).reshape(-1) for v in tb])
-    widths = tuple(widths)
+    # hyper networks: the context columns once per solve, the time column per evaluation; layer-major 1-D tensors (_hyper_layer_major)
+    G_lm, Bb_lm, tg_lm, tb_lm, widths = _hyper_layer_major(block, context)
     e_rows = e.reshape(BT * n, 3)
     # row layout of the (2R, C) tensors of this solve (include/caspr_hip_train.h): blocks of 32 value rows + the tangent rows of the
     # same points when the hidden layers run with the activation in the conv's epilogue (CnfLayer), [values | tangents] otherwise
@@ -813,3 +830,175 @@ def point_cnf_train(flow, x, context, logpx, e=None):
         else:
             x, logpx = layer(x, context, logpx, None, False)
     return x, logpx
+
+
+# ---------------------------------------------------------------------------------------------
+# point CNF block in the SAMPLING direction (cnf.py:70-128 with reverse = True, logpx = None; caspr.py:262 calls it from decode() and
+# the reference differentiates it through torchdiffeq): no Hutchinson tangent, no log-density -- value rows only
+# ---------------------------------------------------------------------------------------------
+class CnfEvalValue(torch.autograd.Function):
+    """One evaluation of the ODE function on value rows as ONE node over the value-only kernels (csrc/backward_flow_value.hip) and the
+    bf16x6 conv / weight-gradient kernels for the two 512 x 512 products.  y (R, 3), then per layer (w, b, gate, beta) with gate / beta
+    (frames, C_l) -> a (R, 3) = dy/dt.  Tape: the two layer products and the three activations, (R, C) each, alive for one evaluation.
+    The (R, C) tensors between the layers hold R rounded up to 128 rows, so that the products run on the bf16x6 conv kernels for every
+    n (ops.conv1x1 takes the f32 kernel otherwise); the value-only kernels touch rows 0..R-1 only and hand the padding rows back as
+    zeros, so they add nothing to a weight gradient (train_ops.py)."""
+
+    @staticmethod
+    def forward(ctx, y, w0, b0, g0, be0, w1, b1, g1, be1, w2, b2, g2, be2, w3, b3, g3, be3, n):
+        if not y.is_cuda:
+            raise ValueError("CnfEvalValue runs on the GPU only (HIP kernels)")
+        R = y.shape[0]
+        y = y.detach().contiguous()
+        b0, g0, be0, b1, g1, be1, b2, g2, be2, b3, g3, be3 = [t_.detach().contiguous() for t_ in (b0, g0, be0, b1, g1, be1, b2, g2, be2, b3, g3, be3)]
+        w0c = w0.detach().contiguous()
+        Rp = (R + 127) // 128 * 128
+        h0 = T.cnf_in_value(y, w0c, b0, g0, be0, n, rows=Rp)
+        z1 = ops.conv1x1_train(_packed(w1, False), None, h0.view(1, Rp, -1)).view(Rp, -1)
+        h1 = T.cnf_act_value(z1, b1, g1, be1, n)
+        z2 = ops.conv1x1_train(_packed(w2, False), None, h1.view(1, Rp, -1)).view(Rp, -1)
+        h2 = T.cnf_act_value(z2, b2, g2, be2, n)
+        zo = ops.conv1x1_train(_packed(w3, False), None, h2.view(1, Rp, -1)).view(Rp, -1)
+        a = T.cnf_out_value(zo, b3, g3, be3, n)
+        ctx.save_for_backward(y, w0c, b0, g0, be0, w1, b1, g1, be1, w2, b2, g2, be2, w3, b3, g3, h0, z1, h1, z2, h2, zo)
+        ctx.n = n
+        return a
+
+    @staticmethod
+    def backward(ctx, da):
+        y, w0, b0, g0, be0, w1, b1, g1, be1, w2, b2, g2, be2, w3, b3, g3, h0, z1, h1, z2, h2, zo = ctx.saved_tensors
+        n, R = ctx.n, y.shape[0]
+        c1, c2 = w1.shape[0], w2.shape[0]
+        dev = y.device
+        rows = lambda t_: t_.view(1, t_.shape[0], t_.shape[1])           # R rounded up to 128 rows; the padding rows of every d* are zero
+        dzo, dg3, dbe3 = T.cnf_out_value_bwd(da.contiguous(), zo, b3, g3, n)
+        dw3 = torch.empty(w3.shape[0], c2, device=dev, dtype=torch.float32)
+        T.conv1x1_wgrad(rows(dzo), rows(h2), c2, w3.shape[0], dw3, None)
+        # last hidden layer: dH = dzo W3 formed inside the activation backward
+        dz2, dg2, dbe2 = T.cnf_act_value_bwd(z2, b2, g2, be2, n, dzo=dzo, wo=w3.detach().contiguous())
+        dw2 = torch.empty(c2, c1, device=dev, dtype=torch.float32)
+        T.conv1x1_wgrad(rows(dz2), rows(h1), c1, c2, dw2, None)
+        dh1 = ops.conv1x1_train(_packed(w2, True), None, rows(dz2))[0]
+        dz1, dg1, dbe1 = T.cnf_act_value_bwd(z1, b1, g1, be1, n, dh=dh1)
+        dw1 = torch.empty(c1, w1.shape[1], device=dev, dtype=torch.float32)
+        T.conv1x1_wgrad(rows(dz1), rows(h0), w1.shape[1], c1, dw1, None)
+        dh0 = ops.conv1x1_train(_packed(w1, True), None, rows(dz1))[0]
+        dy, dw0, dg0, dbe0 = T.cnf_in_value_bwd(y, w0, b0, g0, be0, dh0, n)
+        db = lambda g, dbe: (g * dbe).sum(dim=0)                           # d/db = sum_r da*g = sum_f g[f]*dbeta[f]
+        return (dy, dw0, db(g0, dbe0), dg0, dbe0, dw1, db(g1, dbe1), dg1, dbe1, dw2, db(g2, dbe2), dg2, dbe2, dw3, db(g3, dbe3), dg3, dbe3, None)
+
+
+def _cnf_eval_value(wb, t, y, G_lm, Bb_lm, tg_lm, tb_lm, BT, n, widths):
+    """One evaluation of the ODE function without the Hutchinson term on the value-only kernels: what CnfSampleSolve's reverse sweep
+    rebuilds and differentiates.  wb = (w0, b0, ..., w3, b3); y (BT,n,3) -> a (BT,n,3)."""
+    w0, b0, w1, b1, w2, b2, w3, b3 = wb
+    parts = SplitLayers.apply(torch.sigmoid(G_lm + t * tg_lm), Bb_lm + t * tb_lm, BT, widths)
+    a = CnfEvalValue.apply(y.reshape(BT * n, 3), w0, b0, parts[0], parts[4], w1, b1, parts[1], parts[5], w2, b2, parts[2], parts[6],
+                           w3, b3, parts[3], parts[7], n)
+    return a.view(BT, n, 3)
+
+
+class CnfSampleSolve(torch.autograd.Function):
+    """A CNF block's whole SAMPLING solve (RK4 from t_end down to 0, no divergence) as ONE autograd node with a tape of point-sized
+    tensors: forward = one launch of caspr_cnf_sample_tape_f32, which writes the (BT,n,3) stage input and stage output of every
+    evaluation (24 bytes per point and evaluation) and no layer product; backward = the reverse sweep of CnfBlockSolve for the reversed
+    time axis -- steps S-1..0, stages 4..1, ONE evaluation rebuilt at a time from its stored stage input (_cnf_eval_value), its
+    cotangent pushed through, the results added to preallocated buffers in that fixed order (two runs give the same bits), its tape
+    dropped.  RK4 algebra by hand with h = -t_end / S and stage times t_end + (s + c_i) h; dL/dt_end through h (state update, stage
+    inputs, stage times) and through the start time, accumulated in f64.
+    y (BT,n,3), G_lm / Bb_lm / tg_lm / tb_lm layer-major (_hyper_layer_major), t_end 0-dim tensor, w1x / w2x (ops.pack_cnf_x6), steps,
+    widths, then w0, b0, ..., w3, b3 -> x (BT,n,3)."""
+
+    @staticmethod
+    def forward(ctx, y, G_lm, Bb_lm, tg_lm, tb_lm, t_end, w1x, w2x, steps, widths, *wb):
+        BT, n, _ = y.shape
+        hyper, tcol = _hyper_for_kernel(G_lm, Bb_lm, tg_lm, tb_lm, BT, widths)
+        w0, b0, w1, b1, w2, b2, w3, b3 = [t_.detach().contiguous() for t_ in wb]
+        x, ys, ka = T.cnf_sample_tape(y.detach().contiguous(), hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_end.detach().reshape(1).contiguous(), steps)
+        ctx.save_for_backward(ys, ka, G_lm, Bb_lm, tg_lm, tb_lm, t_end)
+        ctx.steps, ctx.widths, ctx.wb = steps, widths, wb
+        return x
+
+    @staticmethod
+    def backward(ctx, gy):
+        ys, ka, G_lm, Bb_lm, tg_lm, tb_lm, t_end = ctx.saved_tensors
+        S, widths, wb = ctx.steps, ctx.widths, ctx.wb
+        _, _, BT, n, _ = ys.shape
+        dev = ys.device
+        gy = gy.contiguous()
+        t0 = t_end.detach().reshape(())
+        h = -t0 / S                                                    # reversed time axis: t_end -> 0
+        hyp = [v.detach().requires_grad_(True) for v in (G_lm, Bb_lm, tg_lm, tb_lm)]
+        wsel = [i for i, w in enumerate(wb) if w.requires_grad]
+        d_hyp = [torch.zeros_like(v) for v in hyp]
+        d_wb = [torch.zeros_like(w) if w.requires_grad else None for w in wb]
+        dh = torch.zeros((), device=dev, dtype=torch.float64)          # dL/dh and dL/d(start time), summed in f64
+        dt0 = torch.zeros((), device=dev, dtype=torch.float64)
+        dot = lambda u, v: (u.double() * v.double()).sum()
+        CW = (1.0 / 6.0, 2.0 / 6.0, 2.0 / 6.0, 1.0 / 6.0)              # weights of k1..k4 in the RK4 combination
+        TC = (0.0, 0.5, 0.5, 1.0)                                      # stage i: t_end + (s + TC[i]) h, input y + TC[i] h k_{i-1}
+        for s in range(S - 1, -1, -1):
+            k = ka[s]
+            dh += dot(gy, k[0] + 2.0 * k[1] + 2.0 * k[2] + k[3]) / 6.0
+            gy_next, g_in = gy.clone(), None                           # g_in: cotangent of the NEXT stage's input
+            for st in (3, 2, 1, 0):
+                ka_bar = (CW[st] * h) * gy
+                if g_in is not None:
+                    ka_bar = torch.addcmul(ka_bar, g_in, TC[st + 1] * h)
+                with torch.enable_grad():
+                    t = (t0 + (s + TC[st]) * h).detach().requires_grad_(True)
+                    y_in = ys[s, st].detach().requires_grad_(True)
+                    a = _cnf_eval_value(wb, t, y_in, hyp[0], hyp[1], hyp[2], hyp[3], BT, n, widths)
+                    g = torch.autograd.grad(a, [y_in, t] + hyp + [wb[i] for i in wsel], ka_bar)
+                del a
+                g_in = g[0]
+                for buf, gi in zip(d_hyp, g[2:6]):
+                    buf.add_(gi)
+                for i, gi in zip(wsel, g[6:]):
+                    d_wb[i].add_(gi)
+                dt0 += g[1].double()                                   # through the stage time t = t_end + (s + TC) h
+                dh += g[1].double() * (s + TC[st])
+                if st > 0:
+                    dh += TC[st] * dot(g_in, k[st - 1])                # through the stage input y + TC h k_{st-1}
+                gy_next.add_(g_in)
+                del g
+            gy = gy_next
+        dt_end = (dt0 - dh / S).to(t_end.dtype).reshape(t_end.shape)   # h = -t_end / S
+        return (gy, d_hyp[0], d_hyp[1], d_hyp[2], d_hyp[3], dt_end, None, None, None, None) + tuple(d_wb)
+
+
+def cnf_block_sample_train(block, y, context):
+    """One CNF block in the sampling direction, differentiable in y, the context and every parameter of the block: y (BT,n,3),
+    context (BT,zdim) -> x (BT,n,3) at t = 0 after `block.rk4_steps` RK4 steps from sqrt_end_time^2."""
+    layers = block.odefunc.diffeq.layers
+    widths = tuple(l._layer.weight.shape[0] for l in layers)
+    if widths != (512, 512, 512, 3) or block.method != "rk4" or block.frame_steps is not None:
+        raise ValueError("the differentiable sampling solve is built for the 3-512-512-512-3 ODE function on uniform RK4 steps "
+                         "(got widths %s, method %r%s)" % (widths, block.method, ", per-frame step counts" if block.frame_steps is not None else ""))
+    G_lm, Bb_lm, tg_lm, tb_lm, widths = _hyper_layer_major(block, context)
+    t_end = block.sqrt_end_time * block.sqrt_end_time if block.train_T else torch.tensor(float(block.T), device=y.device)
+    w1x, w2x = block._weights_x6()
+    wb = [p_ for l in layers for p_ in (l._layer.weight, l._layer.bias)]
+    x = CnfSampleSolve.apply(y, G_lm, Bb_lm, tg_lm, tb_lm, t_end, w1x, w2x, block.rk4_steps, widths, *wb)
+    block.odefunc._num_evals.fill_(4 * block.rk4_steps)
+    return x
+
+
+def point_cnf_sample_train(flow, y, context):
+    """SequentialFlow in the reverse (sampling) direction (cnf.py:33-48 with reverse = True, logpx = None), differentiable: the chain
+    walked backwards, MovingBatchNorm1d(reverse=True) in torch, every CNF block through CnfSampleSolve.  y (BT,n,3), context (BT,zdim)
+    -> x (BT,n,3).  No fallback: what the route needs is stated in the error."""
+    from ..models.cnf import CNF
+    if not (torch.is_tensor(y) and torch.is_tensor(context) and y.is_cuda and context.is_cuda):
+        raise ValueError("point_cnf_sample_train runs on the GPU only (HIP kernels): y and context must be GPU tensors")
+    if not ops.CNF_BF16X6:
+        raise ValueError("point_cnf_sample_train needs the bf16x6 CNF kernels (ops.CNF_BF16X6 is off)")
+    if not torch.is_grad_enabled():
+        raise ValueError("point_cnf_sample_train records a gradient: it was called with grad mode off (torch.no_grad())")
+    x = y.reshape(-1, y.shape[-2], y.shape[-1]).float()
+    for layer in reversed(flow.chain):
+        if isinstance(layer, CNF):
+            x = cnf_block_sample_train(layer, x, context)
+        else:
+            x = layer(x, context, None, None, True)
+    return x

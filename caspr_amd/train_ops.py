@@ -197,6 +197,166 @@ def cnf_train_fwd(y, logp, e, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_e
     return out, lp_out, ys, ka, knd
 
 
+def cnf_sample_tape(y, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_end, steps):
+    """Sampling solve of one CNF block with its tape in one launch (caspr_cnf_sample_tape_f32): RK4 from t_end down to 0, no divergence.
+    y (BT,n,3), hyper (BT, >= 3078) and tcol as ops.cnf_rk4 takes them, w1x / w2x = ops.pack_cnf_x6, t_end a one-element DEVICE tensor.
+    -> x_0 (BT,n,3), stage inputs ys (steps,4,BT,n,3), stage outputs ka (steps,4,BT,n,3)."""
+    _chk_f32(y, hyper, tcol, w0, b0, b1, b2, w3, b3, t_end)
+    if y.dim() != 3 or y.shape[2] != 3:
+        raise ValueError("cnf_sample_tape: y must be (BT,n,3), got %s" % (tuple(y.shape),))
+    BT, n, _ = y.shape
+    if hyper.dim() != 2 or hyper.shape[0] != BT or hyper.stride(1) != 1 or hyper.shape[1] < 2 * (3 * 512 + 3) or tcol.numel() < 2 * (3 * 512 + 3):
+        raise ValueError("cnf_sample_tape: hyper must be (BT, >= 3078) rows and tcol hold 3078 floats, got %s / %s" % (tuple(hyper.shape), tuple(tcol.shape)))
+    if tuple(w0.shape) != (512, 3) or tuple(w3.shape) != (3, 512) or b0.numel() != 512 or b1.numel() != 512 or b2.numel() != 512 or b3.numel() != 3:
+        raise ValueError("cnf_sample_tape: the kernel is built for the 3-512-512-512-3 ODE function")
+    if w1x is None or w2x is None or w1x.numel() != _lib.load().caspr_cnf_x6_packed_bytes() or w2x.numel() != w1x.numel():
+        raise ValueError("cnf_sample_tape: the bf16x6 weight packs w1x / w2x (ops.pack_cnf_x6) are required")
+    if t_end.numel() != 1 or not t_end.is_cuda or steps <= 0:
+        raise ValueError("cnf_sample_tape: t_end must be a one-element device tensor and steps positive")
+    dev = y.device
+    out = torch.empty(BT, n, 3, device=dev, dtype=torch.float32)
+    ys = torch.empty(steps, 4, BT, n, 3, device=dev, dtype=torch.float32)
+    ka = torch.empty(steps, 4, BT, n, 3, device=dev, dtype=torch.float32)
+    with ops.timed("cnf_sample_tape"):
+        _lib.check(_lib.load().caspr_cnf_sample_tape_f32(_p(y), _p(hyper), hyper.stride(0), _p(tcol), _p(w0), _p(b0), _p(w1x), _p(b1), _p(w2x), _p(b2),
+                                                         _p(w3), _p(b3), 512, _p(t_end), int(steps), _p(out), _p(ys), _p(ka), BT, n, _stream()),
+                   "caspr_cnf_sample_tape_f32")
+    return out, ys, ka
+
+
+# ---- the gated softplus layers on value rows only (csrc/backward_flow_value.hip): R = frames * n rows, point p in row p.
+# gate / beta (frames, C) contiguous; the backward wrappers return dgate / dbeta (frames, C) with the point splits already summed.
+# The (rows, C) tensors may hold MORE than R rows: the caller rounds the row count up (to the 128 rows the bf16x6 conv kernels want of
+# the products between these layers).  The kernels read and write rows 0..R-1 only; every wrapper that returns such a tensor hands its
+# padding rows back as zeros, so that they add nothing to a weight gradient taken over all rows.
+def _chk_value(name, gate, n, *rows):
+    _chk_f32(gate)
+    R = gate.shape[0] * n
+    for t in rows:
+        if t is None:
+            continue
+        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) % 4 != 0 or t.data_ptr() % 16 != 0:
+            raise ValueError("%s: (rows, C) float32 GPU tensors with unit column stride, a row stride that is a multiple of 4 and 16-byte alignment are required" % name)
+        if t.shape[0] < R:
+            raise ValueError("%s: %d rows for %d frames of n = %d points" % (name, t.shape[0], gate.shape[0], n))
+    if n <= 0 or R <= 0:
+        raise ValueError("%s: no points (frames %d, n %d)" % (name, gate.shape[0], n))
+    return R
+
+
+def _rows_out(rows, R, C, device):
+    t = torch.empty(rows, C, device=device, dtype=torch.float32)
+    if rows > R:
+        t[R:].zero_()
+    return t
+
+
+def _sum_splits(part, ns):
+    return part[:, 0] if ns == 1 else part.sum(dim=1)
+
+
+def cnf_in_value(y, w0, b, gate, beta, n, rows=None):
+    """H = softplus((W0 y + b) gate[f] + beta[f]); y (R, 3), w0 (C, 3), gate / beta (R / n, C) -> (rows >= R, C), rows past R zero."""
+    _chk_f32(y, w0, b, gate, beta)
+    R, C = y.shape[0], w0.shape[0]
+    rows = R if rows is None else int(rows)
+    if tuple(y.shape) != (R, 3) or tuple(w0.shape) != (C, 3) or C % 4 != 0 or R % n != 0 or tuple(gate.shape) != (R // n, C) or tuple(beta.shape) != (R // n, C) or rows < R:
+        raise ValueError("cnf_in_value: y (R,3), w0 (C,3) with C % 4 == 0, gate / beta (R/n, C) and rows >= R are required")
+    h = _rows_out(rows, R, C, y.device)
+    with ops.timed("k:cnf_in_value", 2):
+        _lib.check(_lib.load().caspr_cnf_in_value_f32(_p(y), _p(w0), _p(b), _p(gate), _p(beta), R, n, C, _p(h), C, _stream()), "caspr_cnf_in_value_f32")
+    return h
+
+
+def cnf_in_value_bwd(y, w0, b, gate, beta, dh, n):
+    """dh (>= R, C) -> dy (R, 3), dW0 (C, 3), dgate (frames, C), dbeta (frames, C)."""
+    R = _chk_value("cnf_in_value_bwd", gate, n, dh)
+    _chk_f32(y, w0, b, beta)
+    C = w0.shape[0]
+    if tuple(y.shape) != (R, 3) or tuple(w0.shape) != (C, 3) or tuple(gate.shape) != (R // n, C) or dh.shape[1] < C:
+        raise ValueError("cnf_in_value_bwd: y (R,3), w0 (C,3), gate / beta (R/n, C), dh (>= R, >= C) are required")
+    L = _lib.load()
+    ns, frames, chunks = L.caspr_cnf_value_splits(n), R // n, (C + 255) // 256
+    dev = y.device
+    dgate = torch.empty(frames, ns, C, device=dev, dtype=torch.float32)
+    dbeta = torch.empty(frames, ns, C, device=dev, dtype=torch.float32)
+    dw_part = torch.empty(frames * ns, C, 3, device=dev, dtype=torch.float32)
+    dy_part = torch.empty(chunks, R, 3, device=dev, dtype=torch.float32)
+    with ops.timed("k:cnf_in_value_bwd", 2):
+        _lib.check(L.caspr_cnf_in_value_bwd_f32(_p(y), _p(w0), _p(b), _p(gate), _p(beta), _p(dh), dh.stride(0), R, n, C, _p(dgate), _p(dbeta), _p(dw_part),
+                                                _p(dy_part), _stream()), "caspr_cnf_in_value_bwd_f32")
+    return dy_part.sum(dim=0), dw_part.sum(dim=0), _sum_splits(dgate, ns), _sum_splits(dbeta, ns)
+
+
+def cnf_act_value(z, b, gate, beta, n):
+    """H = softplus((Z + b) gate[f] + beta[f]) on the columns 0..C-1 of z (rows >= R, >= C), C = b.numel() -> (rows, C), rows past R zero."""
+    R = _chk_value("cnf_act_value", gate, n, z)
+    _chk_f32(b, beta)
+    C = b.numel()
+    h = _rows_out(z.shape[0], R, C, z.device)
+    with ops.timed("k:cnf_act_value", 2):
+        _lib.check(_lib.load().caspr_cnf_act_value_f32(_p(z), z.stride(0), _p(b), _p(gate), _p(beta), R, n, C, _p(h), C, _stream()), "caspr_cnf_act_value_f32")
+    return h
+
+
+def cnf_act_value_bwd(z, b, gate, beta, n, dh=None, dzo=None, wo=None):
+    """Backward of cnf_act_value from dh (>= R, C), or -- the layer in front of the 3-channel output layer -- from dzo (>= R, >= 3) and
+    wo (3, C): dH = dzo wo formed inside the kernel.  -> dz (rows of z, C) with the rows past R zero, dgate (frames, C), dbeta (frames, C)."""
+    R = _chk_value("cnf_act_value_bwd", gate, n, z, dh)
+    _chk_f32(b, beta, wo)
+    if (dh is None) == (dzo is None or wo is None):
+        raise ValueError("cnf_act_value_bwd: give dh, or dzo and wo")
+    C = b.numel()
+    L = _lib.load()
+    ns, frames = L.caspr_cnf_value_splits(n), R // n
+    dev = z.device
+    dz = _rows_out(z.shape[0], R, C, dev)
+    dgate = torch.empty(frames, ns, C, device=dev, dtype=torch.float32)
+    dbeta = torch.empty(frames, ns, C, device=dev, dtype=torch.float32)
+    if dh is not None:
+        with ops.timed("k:cnf_act_value_bwd", 2):
+            _lib.check(L.caspr_cnf_act_value_bwd_f32(_p(z), z.stride(0), _p(b), _p(gate), _p(beta), _p(dh), dh.stride(0), R, n, C, _p(dz), C, _p(dgate),
+                                                     _p(dbeta), _stream()), "caspr_cnf_act_value_bwd_f32")
+    else:
+        if not dzo.is_cuda or dzo.dtype != torch.float32 or dzo.dim() != 2 or dzo.shape[0] < R or dzo.stride(1) != 1 or dzo.shape[1] < 3 or tuple(wo.shape) != (3, C):
+            raise ValueError("cnf_act_value_bwd: dzo must be (>= R, >= 3) float32 GPU rows and wo a contiguous (3, C)")
+        with ops.timed("k:cnf_act_value_bwd_out", 2):
+            _lib.check(L.caspr_cnf_act_value_bwd_out_f32(_p(z), z.stride(0), _p(b), _p(gate), _p(beta), _p(dzo), dzo.stride(0), _p(wo), C, R, n, C, _p(dz), C,
+                                                         _p(dgate), _p(dbeta), _stream()), "caspr_cnf_act_value_bwd_out_f32")
+    return dz, _sum_splits(dgate, ns), _sum_splits(dbeta, ns)
+
+
+def cnf_out_value(zo, b, gate, beta, n):
+    """a (R, 3) = (zo[:R, :3] + b) gate[f] + beta[f]; zo (>= R, >= 3), gate / beta (frames, 3) rows with a common row stride."""
+    _chk_f32(zo, b)
+    R = gate.shape[0] * n
+    if zo.dim() != 2 or zo.shape[0] < R or zo.shape[1] < 3 or gate.stride(1) != 1 or beta.stride(1) != 1 or gate.stride(0) != beta.stride(0) or R <= 0 \
+            or not gate.is_cuda or gate.dtype != torch.float32 or beta.dtype != torch.float32 or tuple(gate.shape) != tuple(beta.shape) or gate.shape[1] != 3:
+        raise ValueError("cnf_out_value: zo (>= R, >= 3), float32 GPU gate / beta (frames, 3) with unit column stride and a common row stride are required")
+    a = torch.empty(R, 3, device=zo.device, dtype=torch.float32)
+    with ops.timed("k:cnf_out_value", 2):
+        _lib.check(_lib.load().caspr_cnf_out_value_f32(_p(zo), zo.stride(0), _p(b), _p(gate), _p(beta), gate.stride(0), R, n, _p(a), _stream()),
+                   "caspr_cnf_out_value_f32")
+    return a
+
+
+def cnf_out_value_bwd(da, zo, b, gate, n):
+    """da (R, 3) -> dzo (rows of zo, 4) (column 3 and the rows past R zero), dgate (frames, 3), dbeta (frames, 3)."""
+    _chk_f32(da, zo, b)
+    R = gate.shape[0] * n
+    if tuple(da.shape) != (R, 3) or zo.dim() != 2 or zo.shape[0] < R or zo.shape[1] < 3 or gate.stride(1) != 1 or gate.shape[1] != 3 or not gate.is_cuda \
+            or gate.dtype != torch.float32:
+        raise ValueError("cnf_out_value_bwd: da must be a contiguous (R, 3), zo (>= R, >= 3), gate float32 GPU (frames, 3) rows with unit column stride")
+    dev = zo.device
+    dzo = _rows_out(zo.shape[0], R, 4, dev)
+    dgate = torch.empty(R // n, 3, device=dev, dtype=torch.float32)
+    dbeta = torch.empty(R // n, 3, device=dev, dtype=torch.float32)
+    with ops.timed("k:cnf_out_value_bwd", 2):
+        _lib.check(_lib.load().caspr_cnf_out_value_bwd_f32(_p(da), _p(zo), zo.stride(0), _p(b), _p(gate), gate.stride(0), R, n, _p(dzo), _p(dgate), _p(dbeta),
+                                                           _stream()), "caspr_cnf_out_value_bwd_f32")
+    return dzo, dgate, dbeta
+
+
 class Segments:
     """CSR of a scatter: for every target row the contributing source rows (ascending) and their weights.
     Built from flat int tensors `target` (nnz), optional `weight` (nnz) and optional `src_rows` (nnz; default: entry e

@@ -202,6 +202,47 @@ int caspr_cnf_train_fwd_f32(const float *y_in, const float *hyper, int ldh, cons
                             int H, const float *t_end, int steps, const float *e, const float *logp_in, float *logp_out,
                             float *y_out, float *ys, float *ka, float *knd, int BT, int n, void *stream);
 
+/* The SAMPLING solve of one point-CNF block with the tape its gradient needs (csrc/ode_sample_tape.hip; train/flow_grad.py:
+ * CnfSampleSolve) -- the reference's cnf.py:70-128 with reverse = True and logpx = None, which caspr.py:262 runs in decode() and
+ * differentiates through torchdiffeq: `steps` classic RK4 steps from *t_end DOWN to 0 (h = -t_end / steps), no divergence, ONE launch,
+ * the 64-point bf16x6 evaluation of caspr_cnf_rk4_x6_f32 (same hyper / tcol columns, same packs w1x / w2x of caspr_pack_weight_cnf_x6;
+ * H = 512).  t_end: one float in DEVICE memory.  No MovingBatchNorm at either end.  Writes y_out (BT,n,3) and every evaluation's stage
+ * input ys (steps,4,BT,n,3) and stage output ka (steps,4,BT,n,3) = dy/dt: 24 bytes per point and evaluation, no 512-wide tensor.
+ * Any n >= 1 (the columns of a partial workgroup write nothing).  A frame's results do not depend on the batch around it.          */
+int caspr_cnf_sample_tape_f32(const float *y_in, const float *hyper, int ldh, const float *tcol, const float *w0, const float *b0,
+                              const void *w1x, const float *b1, const void *w2x, const float *b2, const float *w3, const float *b3,
+                              int H, const float *t_end, int steps, float *y_out, float *ys, float *ka, int BT, int n, void *stream);
+
+/* The gated softplus layers of the ODE function on VALUE rows only (csrc/backward_flow_value.hip), for the reverse sweep of the
+ * sampling solve above (cnf.py:70-128 with logpx = None, caspr.py:262: no Hutchinson tangent, no log-density): R = frames n rows,
+ * point p in row p, frame f = p / n; C % 4 == 0; b, gate, beta, Z, H, dH, dZ 16-byte aligned with row strides that are multiples
+ * of 4.  Any n >= 1: there are no padding rows.  ns = caspr_cnf_value_splits(n) point splits per frame in the backward entries:
+ * dgate / dbeta come as partials (frames, ns, C) the caller sums over ns; every sum runs in a fixed order (no atomics).
+ *   first layer   H = softplus((W0 y + b) gate[f] + beta[f]), Y (R,3), W0 (C,3); backward also dW0_part (frames ns, C, 3) (sum =
+ *                 dW0; db = sum_f gate dbeta) and dY_part (ceil(C/256), R, 3) = per-chunk partial sums of dL/dy
+ *   hidden        H = softplus((Z + b) gate[f] + beta[f]) on a given product Z (R, ldz); backward dZ (R, lddz) from dH, or (_out: the
+ *                 layer in front of the 3-channel output layer, odefunc.py:103) from dH = dZo Wo formed on the fly, dZo (R, ldo >= 3),
+ *                 Wo (3, ldw >= C)
+ *   output        a (R,3) = (Zo + b) gate[f] + beta[f], gate / beta rows of a (frames, ldg) tensor; backward dZo (R, 4) (column 3
+ *                 zero), dgate / dbeta (frames, 3)                                                                              */
+int caspr_cnf_value_splits(int n);
+int caspr_cnf_in_value_f32(const float *Y, const float *W0, const float *b, const float *gate, const float *beta, long R, int n,
+                           int C, float *H, int ldh, void *stream);
+int caspr_cnf_in_value_bwd_f32(const float *Y, const float *W0, const float *b, const float *gate, const float *beta,
+                               const float *dH, int ldd, long R, int n, int C, float *dgate, float *dbeta, float *dW0_part,
+                               float *dY_part, void *stream);
+int caspr_cnf_act_value_f32(const float *Z, int ldz, const float *b, const float *gate, const float *beta, long R, int n, int C,
+                            float *H, int ldh, void *stream);
+int caspr_cnf_act_value_bwd_f32(const float *Z, int ldz, const float *b, const float *gate, const float *beta, const float *dH,
+                                int ldd, long R, int n, int C, float *dZ, int lddz, float *dgate, float *dbeta, void *stream);
+int caspr_cnf_act_value_bwd_out_f32(const float *Z, int ldz, const float *b, const float *gate, const float *beta,
+                                    const float *dZo, int ldo, const float *Wo, int ldw, long R, int n, int C, float *dZ,
+                                    int lddz, float *dgate, float *dbeta, void *stream);
+int caspr_cnf_out_value_f32(const float *Zo, int ldo, const float *b, const float *gate, const float *beta, int ldg, long R,
+                            int n, float *A, void *stream);
+int caspr_cnf_out_value_bwd_f32(const float *dA, const float *Zo, int ldo, const float *b, const float *gate, int ldg, long R,
+                                int n, float *dZo, float *dgate, float *dbeta, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
