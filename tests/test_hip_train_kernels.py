@@ -7,6 +7,9 @@ by softplus (oracle/model.py: odenet), and the tangent / divergence rows come fr
 the whole block, from the oracle's GRAD_MODE double backward -- never from the closed form sigmoid(a) * ad.  Every check is
 max |hip - f64| / max |f64| per tensor, measured and recorded by test_hip_train.rel: every error and its bound land in that
 module's JSON report, keyed "kernels:<case>:<tensor>".
+
+The encoder's GroupNorm / max / column-sum kernels, the skinny and in_relu_from routes of conv1x1_wgrad and the value-only CNF layers
+(csrc/backward_flow_value.hip) are not covered here: tests/test_hip_train_edges.py runs them one by one at their edges ("edges:" keys).
 """
 import numpy as np
 import pytest
@@ -23,13 +26,15 @@ FWD, GRAD = 1e-5, 5e-5          # starting bounds of every check (relative to th
 class Checks:
     """Collects every comparison of one test (so that the report holds all of them even when one fails) and asserts at the end."""
 
+    prefix = "kernels"
+
     def __init__(self, tag):
         self.tag, self.bad = tag, []
 
     def __call__(self, name, got, want, bound, ref=None):
         assert bound <= 2e-4, "no bound above the full-step L2 bound"
         try:
-            rel("kernels:%s:%s" % (self.tag, name), got, want, bound, ref=ref)
+            rel("%s:%s:%s" % (self.prefix, self.tag, name), got, want, bound, ref=ref)
         except AssertionError as e:
             self.bad.append(str(e))
 
