@@ -8,6 +8,7 @@ tensor must live on a HIP device -- there is no CPU fallback (calls raise instea
 Layouts: activations are point-major (B, P, C) float32 with row stride = last-dim size unless a
 leading-dimension is given; index tensors are int32.
 """
+import contextlib
 import ctypes
 
 import torch
@@ -413,34 +414,163 @@ class PackedWeight:
 CONV_ROW_INVARIANT = 0x100     # include/caspr_hip.h: act flag
 
 
-# The f16x3 conv's range guard (csrc/gemm_f16x3w.hip): an input value that is not finite in f16 after the 2^4 scale makes its row NaN and
-# ORs into a status word.  One word per (device, stream), never cleared by a launch: it is copied to pinned host memory behind a conv when
-# no earlier copy is still outstanding (eight wide layers per encoder pass would otherwise queue eight copies), read when that copy has
-# arrived -- at the next f16x3 conv on the stream, or by check_deferred_errors, which first fetches what the skipped copies would have
-# shown -- and cleared once it has been reported.
-_c3_status = {}          # stream key -> [(pinned host tensor, event)], at most one
-_c3_pool = []
-_c3_word = {}            # stream key -> (device word, the torch stream it belongs to)
-_c3_stale = set()        # stream keys with launches behind the last copy
-CONV_ROUTE_COUNT = {"h3w": 0}      # launches of the f16x3 entries so far (tests assert the route from it)
+# ---------------------------------------------------------------------------------------------
+# The deferred status channel.  A kernel-side failure (a team barrier that gave up, a used-up attempt budget, a range guard, a capped
+# frame, an accuracy check above its tolerance) is a status on the device.  Reading it right away would put a host synchronisation
+# back into the path, so it is copied to pinned host memory behind the launch and examined once that copy has arrived: at the next
+# call of the same kind on the stream, or when the caller asks (check_deferred_errors, e.g. after a synchronize).  One record per
+# launch, never overwritten before it has been read: a failed launch followed by a clean one still raises.
+# The two functions below (and _zero_word) are all that touches the device; the CPU test of the channel replaces them.
+# ---------------------------------------------------------------------------------------------
+def _pinned(n, dtype):
+    return torch.empty(n, dtype=dtype).pin_memory()
 
 
-def _c3_raise_if_failed(key, wait=False):
-    ring = _c3_status.get(key)
-    failed = False
-    while ring:
-        host, ev = ring[0]
-        if wait:
-            ev.synchronize()
-        if not ev.query():
-            break
-        ring.pop(0)
-        failed = failed or int(host[0]) != 0
-        _c3_pool.append(host)
-    if failed:
-        word, stream = _c3_word[key]
+def _copy_behind(host, src, stream=None):
+    """host <- src behind the work queued on `stream` (None: the current one) -> the event that tells when it has arrived."""
+    ev = torch.cuda.Event()
+    if stream is None:
+        host.copy_(src, non_blocking=True)
+        ev.record(torch.cuda.current_stream())
+    else:
         with torch.cuda.stream(stream):
-            word.zero_()                               # reported: the next call starts clean
+            host.copy_(src, non_blocking=True)
+            ev.record(stream)
+    return ev
+
+
+class _Deferred:
+    """One channel: report(records) raises or warns from the arrived records [(values, meta)], oldest first, values = the copied
+    words as a Python list."""
+    BACKLOG = 64         # records outstanding on one key before a post blocks on the oldest
+
+    def __init__(self, report):
+        self.report = report
+        self.rings = {}      # key -> [(pinned host tensor, event, meta)], oldest first
+        self.pool = {}       # (dtype, numel) -> pinned tensors that have been read and may be reused
+
+    @staticmethod
+    def key(device):
+        return (device.index, torch.cuda.current_stream().cuda_stream)
+
+    def post(self, key, src, meta=None, stream=None):
+        ring = self.rings.setdefault(key, [])
+        if len(ring) >= self.BACKLOG:                # nobody drained: bound the backlog (blocks on the oldest; a failure raises from here)
+            ring[0][1].synchronize()
+            self.poll(key)
+        free = self.pool.get((src.dtype, src.numel()))
+        host = free.pop() if free else _pinned(src.numel(), src.dtype)     # no fill value: the copy overwrites all of it
+        ring.append((host, _copy_behind(host, src, stream), meta))
+
+    def poll(self, key, wait=False):
+        """Drain the records of `key` whose copy has arrived (all of them with wait=True), up to the first that has not, and report."""
+        ring = self.rings.get(key)
+        if not ring:
+            return
+        records = []
+        while ring:
+            host, ev, meta = ring[0]
+            if wait:
+                ev.synchronize()
+            if not ev.query():
+                break
+            ring.pop(0)
+            records.append((host.tolist(), meta))
+            self.pool.setdefault((host.dtype, host.numel()), []).append(host)
+        if records:
+            self.report(records)
+
+    def poll_all(self, wait=False):
+        for key in list(self.rings):
+            self.poll(key, wait)
+
+    def on(self, device):
+        """with channel.on(device) as status: <launch>; status.post(src, meta)  -- reports what has arrived of the stream's earlier
+        launches first, without waiting.  Under stream capture it does neither: no event queries, no host copies there."""
+        return _DeferredScope(self, device)
+
+
+class _DeferredScope:
+    __slots__ = ("chan", "device", "key", "live")
+
+    def __init__(self, chan, device):
+        self.chan, self.device = chan, device
+
+    def __enter__(self):
+        self.key = self.chan.key(self.device)
+        self.live = not torch.cuda.is_current_stream_capturing()
+        if self.live:
+            self.chan.poll(self.key)
+        return self
+
+    def __exit__(self, *exc):
+        return False
+
+    def post(self, src=None, meta=None):
+        if self.live:
+            self.chan.post(self.key, src, meta)
+
+    @property
+    def word(self):
+        return self.chan.word(self.key, self.device)
+
+
+class _DeferredWord(_Deferred):
+    """A channel whose kernels report into one persistent int32 device word per (device, stream)."""
+
+    def __init__(self, report):
+        super().__init__(report)
+        self.words = {}      # key -> (device word, the torch stream it belongs to)
+
+    def word(self, key, device):
+        ent = self.words.get(key)
+        if ent is None:
+            ent = self.words[key] = (torch.zeros(1, device=device, dtype=torch.int32), torch.cuda.current_stream())
+        return ent[0]
+
+
+def _zero_word(word, stream):
+    with torch.cuda.stream(stream):
+        word.zero_()
+
+
+class _DeferredSticky(_DeferredWord):
+    """The word is never cleared by a launch, so one copy shows every trip before it: a post behind an outstanding copy only marks the
+    stream stale (eight wide layers per encoder pass would otherwise queue eight copies), a waiting poll first fetches what the
+    skipped copies would have shown, and the word is cleared, on its own stream, once a trip has been reported."""
+
+    def __init__(self, report):
+        super().__init__(report)
+        self.stale = set()   # keys with launches behind the last copy
+
+    def post(self, key, src=None, meta=None):
+        if self.rings.get(key):
+            self.stale.add(key)
+        else:
+            self._fetch(key)
+
+    def _fetch(self, key):
+        word, stream = self.words[key]
+        super().post(key, word, None, stream)
+        self.stale.discard(key)
+
+    def poll(self, key, wait=False):
+        try:
+            if wait and key in self.stale and not self.rings.get(key):
+                self._fetch(key)
+            super().poll(key, wait)
+            if wait and key in self.stale:             # launches behind the copy that was outstanding
+                self._fetch(key)
+                super().poll(key, True)
+        except _lib.CasprHipError:
+            _zero_word(*self.words[key])               # reported: the next call starts clean
+            raise
+
+
+# The f16x3 conv's range guard (csrc/gemm_f16x3w.hip): an input value that is not finite in f16 after the 2^4 scale makes its row NaN and
+# ORs into the stream's sticky status word.
+def _conv_h3_report(records):
+    if any(words[0] for words, _ in records):
         raise _lib.CasprHipError("caspr_conv1x1_h3w_f32: the range guard of the f16x3 pointwise conv tripped: an input activation (after the "
                                  "producer's GroupNorm / ReLU) reached 4095 in magnitude or was not finite, which f16 cannot hold after the kernel's "
                                  "2^4 prescale; the outputs of the affected rows were set to NaN.  Remedy: conv_split=\"bf16x6\" "
@@ -448,52 +578,17 @@ def _c3_raise_if_failed(key, wait=False):
                                  "exponent range")
 
 
-def _c3_fetch(key):
-    word, stream = _c3_word[key]
-    host = _c3_pool.pop() if _c3_pool else torch.zeros(1, dtype=torch.int32).pin_memory()
-    ev = torch.cuda.Event()
-    with torch.cuda.stream(stream):
-        host.copy_(word, non_blocking=True)
-        ev.record(stream)
-    _c3_status.setdefault(key, []).append((host, ev))
-    _c3_stale.discard(key)
+_conv_h3 = _DeferredSticky(_conv_h3_report)
+CONV_ROUTE_COUNT = {"h3w": 0}      # launches of the f16x3 entries so far (tests assert the route from it)
 
 
-def _c3_drain(key, wait=False):
-    if wait and key in _c3_stale and not _c3_status.get(key):
-        _c3_fetch(key)
-    _c3_raise_if_failed(key, wait=wait)
-    if wait and key in _c3_stale:                      # launches behind the copy that was outstanding
-        _c3_fetch(key)
-        _c3_raise_if_failed(key, wait=True)
-
-
-class _c3_launch:
-    """with _c3_launch(x) as word: <launch an f16x3 conv that ORs into word>  -- reports an earlier launch's trip first (never under
-    stream capture: no event queries, no host copies there)."""
-
-    def __init__(self, x):
-        self.dev = x.device
-
-    def __enter__(self):
-        stream = torch.cuda.current_stream()
-        self.key = (self.dev.index, stream.cuda_stream)
-        self.capturing = torch.cuda.is_current_stream_capturing()
-        if not self.capturing:
-            _c3_raise_if_failed(self.key)
-        CONV_ROUTE_COUNT["h3w"] += 1
-        ent = _c3_word.get(self.key)
-        if ent is None:
-            ent = _c3_word[self.key] = (torch.zeros(1, device=self.dev, dtype=torch.int32), stream)
-        return _p(ent[0])
-
-    def __exit__(self, *exc):
-        if exc[0] is None and not self.capturing:
-            if _c3_status.get(self.key):
-                _c3_stale.add(self.key)
-            else:
-                _c3_fetch(self.key)
-        return False
+@contextlib.contextmanager
+def _conv_h3_launch(x):
+    """with _conv_h3_launch(x) as word: <launch an f16x3 conv that ORs into word>  -- reports an earlier launch's trip first."""
+    CONV_ROUTE_COUNT["h3w"] += 1
+    with _conv_h3.on(x.device) as status:
+        yield _p(status.word)
+        status.post()
 
 
 def _conv_h3w(split):
@@ -524,7 +619,7 @@ def conv1x1(pw, bias, x, bbias=None, in_scale=None, in_shift=None, in_relu=False
     if CONV_BF16X6 and CONV_X6W and pw.x6w_ok and P % 128 == 0 and not row_invariant and in_relu_from % 8 == 0 and act == 0 and _x6w_fills(pw, B, P):
         if _conv_h3w(split):
             main, tail = pw.xh()
-            with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, pw.cout, B * P), 2), _c3_launch(x) as word:
+            with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, pw.cout, B * P), 2), _conv_h3_launch(x) as word:
                 _lib.check(_lib.load().caspr_conv1x1_h3w_f32(_p(main), _p(tail), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
                                                              int(in_relu_from), _p(out), ldy, B, P, pw.cin, pw.cout, 0, None, None, 0.0, None, None, None,
                                                              None, None, None, 0, word, _stream()), "caspr_conv1x1_h3w_f32")
@@ -613,7 +708,7 @@ def conv1x1_gn(pw, bias, x, gamma, beta, groups=16, eps=1e-5, want_max=False, wa
     h3w = _conv_h3w(split)
     if pool > 1 and CONV_X6W and pw.x6w_ok and _x6w_fills(pw, B, P) and h3w:
         main, tail = pw.xh()
-        with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, C, B * P), 2), _c3_launch(x) as word:
+        with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, C, B * P), 2), _conv_h3_launch(x) as word:
             _lib.check(L.caspr_conv1x1_h3w_pooled_f32(_p(main), _p(tail), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
                                                       int(in_relu_from), _p(y), ldy, B, P, pw.cin, C, groups, int(pool), _p(gamma), _p(beta), float(eps),
                                                       _p(scale), _p(shift), _p(pmax), _p(mean), _p(rstd), _p(ws), ws.numel(), word, _stream()),
@@ -651,7 +746,7 @@ def conv1x1_gn(pw, bias, x, gamma, beta, groups=16, eps=1e-5, want_max=False, wa
         return res
     if CONV_X6W and pw.x6w_ok and _x6w_fills(pw, B, P) and h3w:
         main, tail = pw.xh()
-        with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, C, B * P), 2), _c3_launch(x) as word:
+        with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, C, B * P), 2), _conv_h3_launch(x) as word:
             _lib.check(L.caspr_conv1x1_h3w_f32(_p(main), _p(tail), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
                                                int(in_relu_from), _p(y), ldy, B, P, pw.cin, C, groups, _p(gamma), _p(beta), float(eps),
                                                _p(scale), _p(shift), _p(pmax), _p(mean), _p(rstd), _p(ws), ws.numel(), word, _stream()),
@@ -727,7 +822,7 @@ def conv1x1_gn_early(pw, bias, x, gamma, beta, on_early, groups=16, eps=1e-5, in
 
     def part(mt0, mt1, with_tail, reserve):
         if h3w:
-            with _c3_launch(x) as word:
+            with _conv_h3_launch(x) as word:
                 _lib.check(L.caspr_conv1x1_h3w_part_f32(_p(main), _p(tail), _p(bias), None, _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
                                                         int(in_relu_from), _p(y), ldy, B, P, pw.cin, C, mt0, mt1, int(with_tail), int(reserve), _p(ws),
                                                         ws.numel(), word, _stream()), "caspr_conv1x1_h3w_part_f32")
@@ -793,7 +888,7 @@ def conv1x1_gn_tail_beside(pw, bias, x, gamma, beta, tail_stream, groups=16, eps
 
     def part(mt0, mt1, with_tail):
         if h3w:
-            with _c3_launch(x) as word:
+            with _conv_h3_launch(x) as word:
                 _lib.check(L.caspr_conv1x1_h3w_part_f32(_p(main), _p(tail), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
                                                         int(in_relu_from), _p(y), ldy, B, P, pw.cin, C, mt0, mt1, int(with_tail), 0, _p(ws), ws.numel(),
                                                         word, _stream()), "caspr_conv1x1_h3w_part_f32")
@@ -906,35 +1001,25 @@ def _team_workspace(nbytes, device):
 
 
 # A team barrier that gives up (its workgroups were not co-resident within the spin bound) poisons the solve's output with
-# NaN and sets an error word in the workspace.  Reading that word right away would put a host synchronisation back into
-# the path, so it is copied to pinned host memory behind the kernel and examined once that copy has completed: at the
-# next solve on the same stream, or when the caller asks (check_deferred_errors, e.g. after a synchronize).
-_team_status = {}
+# NaN and sets an error word per group of 16 sequences in the workspace.
 _LM_WS_STRIDE_WORDS = (256 + (2 * 128 * 16 * 4 + 32 * 4 * 256) * 4) // 4      # LM_WS_STRIDE of csrc/ode.hip, in 32-bit words
 
 
-_team_pool = []          # pinned status buffers that have been read and may be reused
+def _team_words(ws, B):
+    """The error word of each group of the team kernel's workspace, as a strided int32 view."""
+    groups = (B + 15) // 16
+    return ws[:groups * _LM_WS_STRIDE_WORDS * 4].view(torch.int32)[16::_LM_WS_STRIDE_WORDS]
 
 
-def _team_raise_if_failed(key, wait=False):
-    """Drain every status record of this stream whose copy has completed (all of them with wait=True), oldest first; one record
-    per solve, never overwritten before it has been read: a failed solve followed by a successful one still raises."""
-    ring = _team_status.get(key)
-    failed = False
-    while ring:
-        host, ev = ring[0]
-        if wait:
-            ev.synchronize()
-        if not ev.query():
-            break
-        ring.pop(0)
-        failed = failed or int(host.max()) != 0
-        _team_pool.append(host)
-    if failed:
+def _team_report(records):
+    if any(any(words) for words, _ in records):
         raise _lib.CasprHipError("caspr_latent_rk4_team_f32: a team barrier gave up (the 32 x ceil(B/16) workgroups were not co-resident "
                                  "within the spin bound); the solve's output was poisoned with NaN.  Set caspr_amd.ops.LATENT_TEAM = False "
                                  "(config.latent_team; it also takes the early solve of reconstruct() off the team kernel) to use the "
                                  "single-workgroup kernel when other streams / processes saturate the GPU")
+
+
+_team = _Deferred(_team_report)
 
 
 def check_deferred_errors(wait=True):
@@ -942,33 +1027,21 @@ def check_deferred_errors(wait=True):
     latent solve's attempt budget, the range guard of the f16x3 CNF solve or of the f16x3 convs, a frame capped by the per-frame step controller), or
     CasprAccuracyError / warn if a run-time accuracy check of the fixed-step integrators came back above its tolerance
     (guard_track).  wait=True blocks until the status words of every outstanding solve / check have arrived."""
-    for key in list(_team_status):
-        _team_raise_if_failed(key, wait=wait)
-    for key in list(_dp5_status):
-        _dp5_raise_if_failed(key, wait=wait)
-    for key in list(_h3_status):
-        _h3_raise_if_failed(key, wait=wait)
-    for key in list(_c3_word):
-        _c3_drain(key, wait=wait)
-    for key in list(_steps_status):
-        _steps_raise_if_capped(key, wait=wait)
-    _guard_drain(wait=wait)
+    for chan in (_team, _latent_dp5, _cnf_h3, _conv_h3, _steps, _guard):
+        chan.poll_all(wait)
 
 
 # ---------------------------------------------------------------------------------------------
 # Run-time accuracy guard of the fixed-step integrators (models/caspr.py: CaSPR.check_tol).  The reference's dopri5 bounds its
 # integration error at every call (flow.py:96-99, cnf.py:100-119, latent_ode_model.py:38,83); a fixed step count does not.  With the
 # guard on, every solve is repeated on a subsample at half (or twice) the step count on a side stream, the two results are compared
-# ON THE DEVICE, and the maximum difference travels to pinned host memory behind the comparison -- the same deferred channel as the
-# team kernel's error word: no host synchronisation in the path; the verdict is read at the next guarded call or by
+# ON THE DEVICE, and the maximum difference travels through the deferred channel: the verdict is read at the next guarded call or by
 # check_deferred_errors().
 # ---------------------------------------------------------------------------------------------
 class CasprAccuracyError(_lib.CasprHipError):
     """A guarded RK4 solve whose step-halving error estimate exceeds the tolerance asked for (CaSPR.check_tol)."""
 
 
-_guard_ring = []         # [(pinned host tensor, event, meta)], oldest first
-_guard_pool = []
 GUARD_LAST = {}          # name -> the last drained record {"diff", "estimate", "tol", "steps", "other_steps", "ok"}
 GUARD_HISTORY_MAX = 0.0  # largest estimate / tol ratio seen since reset_guard()
 
@@ -984,30 +1057,16 @@ def guard_track(diff, scale, meta):
     {"name", "tol", "factor", "steps", "other_steps", "action", "what"} -- estimate = factor * diff is compared with
     tol * (1 + scale), i.e. torchdiffeq's  atol + rtol |x|  with atol = rtol = tol (what the reference sets: flow.py:96-99,
     latent_ode_model.py:83), when the copy has arrived."""
-    if len(_guard_ring) >= 64:                      # nobody drained for 64 checks: bound the backlog (blocks on the oldest)
-        _guard_ring[0][1].synchronize()
-    _guard_drain(wait=False)
-    host = _guard_pool.pop() if _guard_pool else torch.zeros(2, dtype=torch.float32).pin_memory()
-    host.copy_(torch.stack([diff.reshape(()), scale.reshape(())]), non_blocking=True)
-    ev = torch.cuda.Event()
-    ev.record(torch.cuda.current_stream())
-    _guard_ring.append((host, ev, meta))
+    _guard.poll_all()
+    _guard.post(None, torch.stack([diff.reshape(()), scale.reshape(())]), meta)      # one ring for all streams: key None
 
 
-def _guard_drain(wait=False):
+def _guard_report(records):
     import math
     import warnings
     global GUARD_HISTORY_MAX
     failed = []
-    while _guard_ring:
-        host, ev, meta = _guard_ring[0]
-        if wait:
-            ev.synchronize()
-        if not ev.query():
-            break
-        _guard_ring.pop(0)
-        d, xmax = float(host[0]), float(host[1])
-        _guard_pool.append(host)
+    for (d, xmax), meta in records:
         est = meta["factor"] * d
         bound = meta["tol"] * (1.0 + xmax) if math.isfinite(xmax) else meta["tol"]
         ok = math.isfinite(est) and est <= bound
@@ -1020,27 +1079,14 @@ def _guard_drain(wait=False):
                    "it by step doubling) or the tolerance." % (meta["what"], meta["steps"], meta["steps"], meta["other_steps"], d, est, bound,
                                                               meta["tol"], xmax))
             if meta["action"] == "warn":
-                warnings.warn(msg, RuntimeWarning, stacklevel=3)
+                warnings.warn(msg, RuntimeWarning, stacklevel=5)      # the caller of guard_track / check_deferred_errors: above poll_all, poll and this
             else:
                 failed.append(msg)
     if failed:
         raise CasprAccuracyError("; ".join(failed))
 
 
-def _team_track(key, ws, B):
-    """Queue the team kernel's error words (one per group of 16 sequences) for a later, non-blocking check (_team_raise_if_failed)."""
-    groups = (B + 15) // 16
-    words = ws[:groups * _LM_WS_STRIDE_WORDS * 4].view(torch.int32)[16::_LM_WS_STRIDE_WORDS]      # the error word of each group
-    ring = _team_status.setdefault(key, [])
-    if len(ring) >= 64:                              # nobody drained for 64 solves: bound the backlog (blocks on the oldest)
-        ring[0][1].synchronize()
-        _team_raise_if_failed(key)
-    slot = next((i for i, h in enumerate(_team_pool) if h.numel() == groups), None)
-    host = _team_pool.pop(slot) if slot is not None else torch.zeros(groups, dtype=torch.int32).pin_memory()
-    ev = torch.cuda.Event()
-    host.copy_(words, non_blocking=True)
-    ev.record(torch.cuda.current_stream())
-    ring.append((host, ev))
+_guard = _Deferred(_guard_report)
 
 
 def latent_rk4(z0, times, steps, wts, team=None):
@@ -1061,16 +1107,12 @@ def latent_rk4(z0, times, steps, wts, team=None):
     L = _lib.load()
     if (LATENT_TEAM if team is None else team) and H == 512 and D <= 64 and B <= 64:
         # 32 workgroups per 16 sequences with LDS-resident weights (csrc/ode.hip): the serial chain runs ~3x faster
-        key = (z0.device.index, torch.cuda.current_stream().cuda_stream)
-        capturing = torch.cuda.is_current_stream_capturing()       # hipGraph capture: no event queries, no host copies
-        if not capturing:
-            _team_raise_if_failed(key)                   # status of the previous solve on this stream, if it has arrived
-        with timed("latent_rk4"):
-            ws = _team_workspace(L.caspr_latent_team_ws_bytes(B), z0.device)
-            _lib.check(L.caspr_latent_rk4_team_f32(_p(z0), z0.stride(0), _p(times), B, Tu, D, H, int(steps), *ptrs, _p(out), _p(ws), ws.numel(),
-                                                   _stream()), "caspr_latent_rk4_team_f32")
-        if not capturing:
-            _team_track(key, ws, B)
+        with _team.on(z0.device) as status:
+            with timed("latent_rk4"):
+                ws = _team_workspace(L.caspr_latent_team_ws_bytes(B), z0.device)
+                _lib.check(L.caspr_latent_rk4_team_f32(_p(z0), z0.stride(0), _p(times), B, Tu, D, H, int(steps), *ptrs, _p(out), _p(ws), ws.numel(),
+                                                       _stream()), "caspr_latent_rk4_team_f32")
+            status.post(_team_words(ws, B))
         return out
     with timed("latent_rk4"):
         _lib.check(L.caspr_latent_rk4_f32(_p(z0), z0.stride(0), _p(times), B, Tu, D, H, int(steps), *ptrs, _p(out), _stream()), "caspr_latent_rk4_f32")
@@ -1078,43 +1120,16 @@ def latent_rk4(z0, times, steps, wts, team=None):
 
 
 LATENT_DP5_TRACE_HEAD, LATENT_DP5_TRACE_ROW = 8, 4      # include/caspr_hip.h: the trace layout of caspr_latent_dopri5_f32
-# The adaptive latent solve reports a used-up attempt budget through its `finished` words: copied to pinned memory behind the
-# launch and read when the copy has arrived (the team kernel's channel: the next solve on the stream, or check_deferred_errors).
-_dp5_status = {}         # stream key -> [(pinned host tensor, event, max_attempts)], oldest first
-_dp5_pool = []
+# The adaptive latent solve reports a used-up attempt budget through its `finished` words (B,), posted with max_attempts.
+def _latent_dp5_report(records):
+    for words, budget in records:
+        if not all(words):
+            raise _lib.CasprHipError("caspr_latent_dopri5_f32 (code %d, CASPR_ENOCONV): %d of %d sequences had not reached the last time stamp after "
+                                     "max_attempts = %d attempts; the rows of the stamps they did not reach hold NaN.  Raise max_attempts or the "
+                                     "tolerance" % (-4, words.count(0), len(words), budget))
 
 
-def _dp5_raise_if_failed(key, wait=False):
-    ring = _dp5_status.get(key)
-    failed = None
-    while ring:
-        host, ev, budget = ring[0]
-        if wait:
-            ev.synchronize()
-        if not ev.query():
-            break
-        ring.pop(0)
-        if int(host.min()) == 0 and failed is None:
-            failed = (int((host == 0).sum()), host.numel(), budget)
-        _dp5_pool.append(host)
-    if failed:
-        raise _lib.CasprHipError("caspr_latent_dopri5_f32 (code %d, CASPR_ENOCONV): %d of %d sequences had not reached the last time stamp after "
-                                 "max_attempts = %d attempts; the rows of the stamps they did not reach hold NaN.  Raise max_attempts or the "
-                                 "tolerance" % (-4, failed[0], failed[1], failed[2]))
-
-
-def _dp5_track(key, finished, max_attempts):
-    ring = _dp5_status.setdefault(key, [])
-    if len(ring) >= 64:                              # nobody drained for 64 solves: bound the backlog (blocks on the oldest)
-        ring[0][1].synchronize()
-        _dp5_raise_if_failed(key)
-    n = finished.numel()
-    slot = next((i for i, h in enumerate(_dp5_pool) if h.numel() == n), None)
-    host = _dp5_pool.pop(slot) if slot is not None else torch.ones(n, dtype=torch.int32).pin_memory()
-    ev = torch.cuda.Event()
-    host.copy_(finished, non_blocking=True)
-    ev.record(torch.cuda.current_stream())
-    ring.append((host, ev, max_attempts))
+_latent_dp5 = _Deferred(_latent_dp5_report)
 
 
 def latent_dopri5(z0, times, rtol, atol, wts, max_attempts=1000, return_trace=False):
@@ -1148,15 +1163,11 @@ def latent_dopri5(z0, times, rtol, atol, wts, max_attempts=1000, return_trace=Fa
     trace = torch.empty(B, LATENT_DP5_TRACE_HEAD + LATENT_DP5_TRACE_ROW * max_attempts, device=z0.device, dtype=torch.float32) if return_trace else None
     counters = torch.empty(B, 4, device=z0.device, dtype=torch.int32)
     ptrs = [_p(w.data) if isinstance(w, PackedWeight) else _p(w) for w in wts]
-    key = (z0.device.index, torch.cuda.current_stream().cuda_stream)
-    capturing = torch.cuda.is_current_stream_capturing()           # hipGraph capture: no event queries, no host copies
-    if not capturing:
-        _dp5_raise_if_failed(key)                                  # status of the previous solve on this stream, if it has arrived
-    with timed("latent_dopri5"):
-        _lib.check(_lib.load().caspr_latent_dopri5_f32(_p(z0), z0.stride(0), _p(times), B, Tu, D, H, rtol, atol, max_attempts, *ptrs, _p(out),
-                                                       _p(trace), _p(counters), _stream()), "caspr_latent_dopri5_f32")
-    if not capturing:
-        _dp5_track(key, counters[:, 3], max_attempts)
+    with _latent_dp5.on(z0.device) as status:
+        with timed("latent_dopri5"):
+            _lib.check(_lib.load().caspr_latent_dopri5_f32(_p(z0), z0.stride(0), _p(times), B, Tu, D, H, rtol, atol, max_attempts, *ptrs, _p(out),
+                                                           _p(trace), _p(counters), _stream()), "caspr_latent_dopri5_f32")
+        status.post(counters[:, 3], max_attempts)
     if return_trace:
         return out, {"d0": trace[:, 0], "d1": trace[:, 1], "d2": trace[:, 2], "h0": trace[:, 3], "dt0": trace[:, 4],
                      "attempts": trace[:, LATENT_DP5_TRACE_HEAD:].view(B, max_attempts, LATENT_DP5_TRACE_ROW),
@@ -1191,25 +1202,11 @@ def pack_cnf_h3(w):
 
 
 # The f16x3 solve's range guard (csrc/ode_f16x3w.hip): a hidden activation that is not finite in f16 after the 2^4 scale poisons its
-# point with NaN and sets the launch's status word, which travels like the team kernel's: copied to pinned host memory behind the
-# launch, read when the copy has arrived (the next f16x3 solve on the stream, or check_deferred_errors).
-_h3_status = {}          # stream key -> [(pinned host tensor, event)], oldest first
-_h3_pool = []
-_h3_word = {}            # stream key -> the device word (zeroed by the C entry in front of every launch, copied out behind it)
-
-
-def _h3_raise_if_failed(key, wait=False):
-    ring = _h3_status.get(key)
+# point with NaN and sets the launch's status word (zeroed by the C entry in front of every launch, copied out behind it).
+def _cnf_h3_report(records):
     bits = 0                                         # bit 0: cnf_rk4_h3w_kernel, bit 1: cnf_dp5_h3w_kernel (include/caspr_hip.h)
-    while ring:
-        host, ev = ring[0]
-        if wait:
-            ev.synchronize()
-        if not ev.query():
-            break
-        ring.pop(0)
-        bits |= int(host[0])
-        _h3_pool.append(host)
+    for words, _ in records:
+        bits |= words[0]
     if bits:
         # one error for everything that has arrived: each kernel whose guard tripped is named with its own remedy
         what = []
@@ -1224,16 +1221,7 @@ def _h3_raise_if_failed(key, wait=False):
                                  "f32's exponent range")
 
 
-def _h3_track(key, word):
-    ring = _h3_status.setdefault(key, [])
-    if len(ring) >= 64:                              # nobody drained for 64 solves: bound the backlog (blocks on the oldest)
-        ring[0][1].synchronize()
-        _h3_raise_if_failed(key)
-    host = _h3_pool.pop() if _h3_pool else torch.zeros(1, dtype=torch.int32).pin_memory()
-    ev = torch.cuda.Event()
-    host.copy_(word, non_blocking=True)
-    ev.record(torch.cuda.current_stream())
-    ring.append((host, ev))
+_cnf_h3 = _DeferredWord(_cnf_h3_report)
 
 
 CNF_MAX_TABLE_STEPS = 4096      # include/caspr_hip.h: the largest max_steps of the *_frames_* entries
@@ -1298,26 +1286,20 @@ def cnf_rk4(y, hyper, tcol, w0, b0, w1p, b1, w2p, b2, w3, b3, t_end, steps, reve
         nbytes = _lib.load().caspr_cnf_h3_packed_bytes()
         if w1h.numel() != nbytes or w2h.numel() != nbytes or w1h.dtype != torch.uint8 or w2h.dtype != torch.uint8:
             raise ValueError("cnf_rk4: w1h / w2h must be the packs of pack_cnf_h3")
-        key = (y.device.index, torch.cuda.current_stream().cuda_stream)
-        capturing = torch.cuda.is_current_stream_capturing()       # hipGraph capture: no event queries, no host copies
-        if not capturing:
-            _h3_raise_if_failed(key)                     # status of the previous solves on this stream, if it has arrived
-        word = _h3_word.get(key)
-        if word is None:
-            word = _h3_word[key] = torch.zeros(1, device=y.device, dtype=torch.int32)
-        with timed("cnf_rk4"):
-            if table:
-                _lib.check(_lib.load().caspr_cnf_rk4_h3_frames_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1h), _p(b1), _p(w2h),
-                                                                   _p(b2), _p(w3), _p(b3), w0.shape[0], float(t_end), int(bool(reverse)),
-                                                                   _p(mbn_in), _p(mbn_out), _p(word), _p(out), BT, n, _p(steps), max_steps, _p(order),
-                                                                   _stream()), "caspr_cnf_rk4_h3_frames_f32")
-            else:
-                _lib.check(_lib.load().caspr_cnf_rk4_h3_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1h), _p(b1), _p(w2h),
-                                                            _p(b2), _p(w3), _p(b3), w0.shape[0], float(t_end), int(steps), int(bool(reverse)),
-                                                            _p(mbn_in), _p(mbn_out), _p(word), _p(out), BT, n, _stream()),
-                           "caspr_cnf_rk4_h3_f32")
-        if not capturing:
-            _h3_track(key, word)
+        with _cnf_h3.on(y.device) as status:
+            word = status.word
+            with timed("cnf_rk4"):
+                if table:
+                    _lib.check(_lib.load().caspr_cnf_rk4_h3_frames_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1h), _p(b1), _p(w2h),
+                                                                       _p(b2), _p(w3), _p(b3), w0.shape[0], float(t_end), int(bool(reverse)),
+                                                                       _p(mbn_in), _p(mbn_out), _p(word), _p(out), BT, n, _p(steps), max_steps, _p(order),
+                                                                       _stream()), "caspr_cnf_rk4_h3_frames_f32")
+                else:
+                    _lib.check(_lib.load().caspr_cnf_rk4_h3_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1h), _p(b1), _p(w2h),
+                                                                _p(b2), _p(w3), _p(b3), w0.shape[0], float(t_end), int(steps), int(bool(reverse)),
+                                                                _p(mbn_in), _p(mbn_out), _p(word), _p(out), BT, n, _stream()),
+                               "caspr_cnf_rk4_h3_f32")
+            status.post(word)
         return out
     if table:
         with timed("cnf_rk4"):
@@ -1344,41 +1326,16 @@ def cnf_rk4(y, hyper, tcol, w0, b0, w1p, b1, w2p, b2, w3, b3, t_end, steps, reve
 
 
 # The per-frame step controller (csrc/cnf_frame_steps.hip): a frame that still fails the criterion at the largest rung is CAPPED there.
-# The count of capped frames travels like the f16x3 range guard's word: copied to pinned host memory behind the pilot, read when the
-# copy has arrived (the next pilot on the stream, or check_deferred_errors).
-_steps_status = {}       # stream key -> [(pinned host tensor, event, S_max, tol)], oldest first
-_steps_pool = []
-
-
-def _steps_raise_if_capped(key, wait=False):
-    ring = _steps_status.get(key)
-    msgs = []
-    while ring:
-        host, ev, s_max, tol = ring[0]
-        if wait:
-            ev.synchronize()
-        if not ev.query():
-            break
-        ring.pop(0)
-        if int(host[0]) != 0:
-            msgs.append("%d frame(s) capped at %d steps (tol %.1e)" % (int(host[0]), s_max, tol))
-        _steps_pool.append(host)
+# The count of capped frames is posted behind the pilot, with (S_max, tol).
+def _steps_report(records):
+    msgs = ["%d frame(s) capped at %d steps (tol %.1e)" % (words[0], s_max, tol) for words, (s_max, tol) in records if words[0]]
     if msgs:
         raise CasprAccuracyError("point CNF, per-frame step counts (cnf_steps=\"frame\"): " + "; ".join(msgs) + ": the step-halving estimate of "
                                  "these frames still exceeds tol x (1 + max |x|) at the largest count the controller may choose, and they were "
                                  "solved with it.  Raise cnf_steps_max (a power of two <= 256) or the tolerance")
 
 
-def _steps_track(key, capped, s_max, tol):
-    ring = _steps_status.setdefault(key, [])
-    if len(ring) >= 64:                              # nobody drained for 64 pilots: bound the backlog (blocks on the oldest)
-        ring[0][1].synchronize()
-        _steps_raise_if_capped(key)
-    host = _steps_pool.pop() if _steps_pool else torch.zeros(1, dtype=torch.int32).pin_memory()
-    ev = torch.cuda.Event()
-    host.copy_(capped.sum(dtype=torch.int32).reshape(1), non_blocking=True)
-    ev.record(torch.cuda.current_stream())
-    ring.append((host, ev, s_max, tol))
+_steps = _Deferred(_steps_report)
 
 
 def cnf_steps_update(x_prev, x_cur, P, tol, safety, max_steps, steps, next_tab, capped, stats):
@@ -1440,10 +1397,9 @@ def cnf_frame_steps(run_rung, BT, g, tol, safety=1.2, max_steps=64, device=None)
         cnf_steps_update(x_prev, x_cur, P, tol, safety, max_steps, steps, nxt, capped, stats)
         x_prev, tab, P = x_cur, nxt, 2 * P
     order = cnf_steps_order(steps)
-    if not torch.cuda.is_current_stream_capturing():
-        key = (dev.index, torch.cuda.current_stream().cuda_stream)
-        _steps_raise_if_capped(key)
-        _steps_track(key, capped, max_steps, float(tol))
+    with _steps.on(dev) as status:
+        if status.live:                              # (no reduction in a captured graph either)
+            status.post(capped.sum(dtype=torch.int32).reshape(1), (max_steps, float(tol)))
     pilot = (2 * stats[:, 3] - 1).to(torch.int32)
     return steps, order, {"stats": stats, "capped": capped, "pilot_steps": pilot}
 
@@ -1500,18 +1456,15 @@ def cnf_dopri5(y, hyper, tcol, w0, b0, b1, b2, w3, b3, w1x, w2x, t_end, rtol, at
         nbytes = L.caspr_cnf_h3_packed_bytes()
         if w1h.numel() != nbytes or w2h.numel() != nbytes or w1h.dtype != torch.uint8 or w2h.dtype != torch.uint8:
             raise ValueError("cnf_dopri5: w1h / w2h must be the packs of pack_cnf_h3")
-        key = (y.device.index, torch.cuda.current_stream().cuda_stream)
-        _h3_raise_if_failed(key)                         # status of the previous solves on this stream, if it has arrived
-        word = _h3_word.get(key)
-        if word is None:
-            word = _h3_word[key] = torch.zeros(1, device=y.device, dtype=torch.int32)
-        ws = _workspace(L.caspr_cnf_dopri5_h3_ws_bytes(BT, n, max_attempts), y.device)
-        with timed("cnf_dopri5"):
-            _lib.check(L.caspr_cnf_dopri5_h3_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1h), _p(b1), _p(w2h), _p(b2), _p(w3),
-                                                 _p(b3), w0.shape[0], float(t_end), rtol, atol, max_attempts, int(bool(reverse)), _p(mbn_in),
-                                                 _p(mbn_out), _p(word), _p(out), BT, n, _p(ws), ws.numel(), _p(trace), _p(counters), _stream()),
-                       "caspr_cnf_dopri5_h3_f32")
-        _h3_track(key, word)
+        with _cnf_h3.on(y.device) as status:
+            word = status.word
+            ws = _workspace(L.caspr_cnf_dopri5_h3_ws_bytes(BT, n, max_attempts), y.device)
+            with timed("cnf_dopri5"):
+                _lib.check(L.caspr_cnf_dopri5_h3_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1h), _p(b1), _p(w2h), _p(b2), _p(w3),
+                                                     _p(b3), w0.shape[0], float(t_end), rtol, atol, max_attempts, int(bool(reverse)), _p(mbn_in),
+                                                     _p(mbn_out), _p(word), _p(out), BT, n, _p(ws), ws.numel(), _p(trace), _p(counters), _stream()),
+                           "caspr_cnf_dopri5_h3_f32")
+            status.post(word)
     else:
         ws = _workspace(L.caspr_cnf_dopri5_ws_bytes(BT, n, max_attempts), y.device)
         with timed("cnf_dopri5"):

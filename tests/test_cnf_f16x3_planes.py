@@ -59,7 +59,7 @@ def run_guard(W):
     ops.check_deferred_errors()
     out = launch_h3(W, y, hot, steps, True)
     torch.cuda.synchronize()
-    word = int(ops._h3_word[(0, torch.cuda.current_stream().cuda_stream)].cpu()[0])
+    word = int(ops._cnf_h3.words[(0, torch.cuda.current_stream().cuda_stream)][0].cpu()[0])
     with pytest.raises(_lib.CasprHipError):
         ops.check_deferred_errors()
     return bits(out), word

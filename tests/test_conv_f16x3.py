@@ -71,7 +71,7 @@ def _pieces(ops, dev, pw, b, x, gamma, beta, kw, pieces, reserve=0, groups=16):
     """The layer through caspr_conv1x1_h3w_part_f32 (channel-tile ranges `pieces`, the remainder with the last) + the finalize over all
     groups -> (y, partials, scale, shift, pmax)."""
     from caspr_amd import lib
-    from caspr_amd.ops import _p, _stream, _c3_launch
+    from caspr_amd.ops import _p, _stream, _conv_h3_launch
     L = lib.load()
     B, P_, _ = x.shape
     C = pw.cout
@@ -81,7 +81,7 @@ def _pieces(ops, dev, pw, b, x, gamma, beta, kw, pieces, reserve=0, groups=16):
     scale, shift, pmax = (torch.empty(B, C, device=dev) for _ in range(3))
     main, tail = pw.xh()
     for n, (m0, m1) in enumerate(pieces):
-        with _c3_launch(x) as word:
+        with _conv_h3_launch(x) as word:
             lib.check(L.caspr_conv1x1_h3w_part_f32(_p(main), _p(tail), _p(b), _p(kw["bbias"]), _p(x), x.stride(1), _p(kw["in_scale"]), _p(kw["in_shift"]), 1, 8,
                                                    _p(y), y.stride(1), B, P_, pw.cin, C, m0, m1, int(n == len(pieces) - 1), int(reserve), _p(ws), nb, word,
                                                    _stream()), "caspr_conv1x1_h3w_part_f32")
