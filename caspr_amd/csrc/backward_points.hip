@@ -566,3 +566,78 @@ extern "C" int caspr_segment_sum_f32(const float *src, int lds, int col0, const 
     CASPR_CHECK_LAUNCH("segment_sum");
     return CASPR_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Chamfer backward (gradient of caspr_chamfer_idx_f32's two distance vectors; the loss the reference forms at
+// evaluations.py:40-44 and differentiates through tk3dv's ChamferDistance): with a = idx1[b,i]
+//   dp[b,i] = 2 g1[b,i] (p_i - q_a)  +  sum over j ascending with idx2[b,j] == i of  2 g2[b,j] (p_i - q_j)
+// and dq the mirror image.  No float atomics: a thread owns ONE output point and scans the other direction's index vector of
+// its cloud, tiled through LDS, in ascending order; matches are added in that order in f32 -> bit-reproducible, as
+// segment_sum_kernel above.  One launch: blocks [0, nb1) of grid.x write dp, the rest dq.  An index outside the other cloud
+// (negative: the query had no finite candidate) contributes nothing on either side; nothing is read at it, its g included.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void chamfer_bwd_kernel(const float *__restrict__ p, const float *__restrict__ q, int n, int m,
+                                                          const int32_t *__restrict__ idx1, const int32_t *__restrict__ idx2,
+                                                          const float *__restrict__ g1, const float *__restrict__ g2, int nb1,
+                                                          float *__restrict__ dp, float *__restrict__ dq)
+{
+    __shared__ __attribute__((aligned(16))) int32_t si[1024];
+    const int b = blockIdx.y;
+    const bool second = (int)blockIdx.x >= nb1;
+    const int blk = second ? (int)blockIdx.x - nb1 : (int)blockIdx.x;
+    const int no = second ? m : n, nx = second ? n : m;                      // own / other cloud's point counts
+    const float *own = (second ? q : p) + (long)b * no * 3;
+    const float *oth = (second ? p : q) + (long)b * nx * 3;
+    const int32_t *io = (second ? idx2 : idx1) + (long)b * no;               // own points' nearest neighbours in the other cloud
+    const int32_t *ix = (second ? idx1 : idx2) + (long)b * nx;               // the other cloud's nearest neighbours in this one
+    const float *go = second ? g2 : g1, *gx = second ? g1 : g2;
+    if (go) go += (long)b * no;
+    if (gx) gx += (long)b * nx;
+    float *out = (second ? dq : dp) + (long)b * no * 3;
+    const long i = (long)blk * 256 + threadIdx.x;
+    const bool live = i < no;
+    float x = 0.f, y = 0.f, z = 0.f, ax = 0.f, ay = 0.f, az = 0.f;
+    if (live) {
+        x = own[i * 3]; y = own[i * 3 + 1]; z = own[i * 3 + 2];
+        const int a = io[i];
+        if (go && a >= 0 && a < nx) {
+            const float t = 2.f * go[i];
+            ax = t * (x - oth[(long)a * 3]); ay = t * (y - oth[(long)a * 3 + 1]); az = t * (z - oth[(long)a * 3 + 2]);
+        }
+    }
+    if (gx) {                                                                // (uniform over the launch)
+        const int me = live ? (int)i : -1;                                   // no stored index equals -1 and contributes
+        for (int base = 0; base < nx; base += 1024) {
+            const int cnt = (nx - base) < 1024 ? (nx - base) : 1024;
+            __syncthreads();
+            for (int t = threadIdx.x; t < 1024; t += 256) si[t] = t < cnt ? ix[base + t] : -2;
+            __syncthreads();
+            if (me < 0) continue;
+            for (int j4 = 0; j4 < cnt; j4 += 4) {
+                const int4 v = *reinterpret_cast<const int4 *>(si + j4);
+                const int vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    if (vv[k] == me) {
+                        const long j = base + j4 + k;
+                        const float t = 2.f * gx[j];
+                        ax += t * (x - oth[j * 3]); ay += t * (y - oth[j * 3 + 1]); az += t * (z - oth[j * 3 + 2]);
+                    }
+                }
+            }
+        }
+    }
+    if (live) { out[i * 3] = ax; out[i * 3 + 1] = ay; out[i * 3 + 2] = az; }
+}
+
+extern "C" int caspr_chamfer_bwd_f32(const float *p, const float *q, int B, int n, int m, const int32_t *idx1, const int32_t *idx2,
+                                     const float *g1, const float *g2, float *dp, float *dq, void *stream)
+{
+    CASPR_REQUIRE(p && q && idx1 && idx2 && B > 0 && n > 0 && m > 0, "chamfer_bwd: bad arguments");
+    CASPR_REQUIRE(B <= 65535, "chamfer_bwd: B=%d: the cloud index is grid.y, B <= 65535", B);
+    CASPR_REQUIRE(dp || dq, "chamfer_bwd: dp and dq are both NULL: nothing to compute");
+    const int nb1 = dp ? ceil_div(n, 256) : 0, nb2 = dq ? ceil_div(m, 256) : 0;
+    chamfer_bwd_kernel<<<dim3(nb1 + nb2, B), dim3(256), 0, (hipStream_t)stream>>>(p, q, n, m, idx1, idx2, g1, g2, nb1, dp, dq);
+    CASPR_CHECK_LAUNCH("chamfer_bwd");
+    return CASPR_OK;
+}

@@ -1,0 +1,93 @@
+"""Losses on sampled point clouds with hand-written gradients (include/caspr_hip.h: caspr_chamfer_idx_f32; include/caspr_hip_train.h:
+caspr_chamfer_bwd_f32).
+
+The reference evaluates reconstructions with the Chamfer term of utils/evaluations.py:36-44 (tk3dv ChamferDistance, which carries its
+own CUDA backward).  Here the same term is a differentiable loss on the samples of decode(differentiable=True) /
+reconstruct(differentiable=True): auto-decoding (utils/fit.py), fine-tuning the flow on its samples.  The forward keeps the two
+nearest-neighbour index vectors (4 bytes per point), never an (n, m) matrix; the backward gathers in a fixed order without float
+atomics, so gradients are bit-reproducible.  The approximate EMD (ops.earth_mover_distance) has NO gradient: emd.hip never stores the
+match matrix its gradient would need.  Same rules as ops.py: float32 contiguous GPU tensors, no CPU fallback.
+"""
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import ops
+from . import train_ops
+
+
+def _chk_cloud(fn, name, t):
+    """`name` = the argument as the caller wrote it: every refusal says which tensor it is about.  Shape, type and layout first, the
+    device last (_chk_gpu), so that what is wrong with a tensor is reported wherever it lives."""
+    if not torch.is_tensor(t) or t.dim() != 3 or t.shape[2] != 3:
+        raise ValueError("%s: %s must be a (F,N,3) tensor, got %s" % (fn, name, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+    if t.dtype != torch.float32:
+        raise ValueError("%s: %s must be float32, got %s" % (fn, name, t.dtype))
+    if not t.is_contiguous():
+        raise ValueError("%s: %s must be contiguous (call .contiguous())" % (fn, name))
+
+
+def _chk_gpu(fn, name, t):
+    if not t.is_cuda:
+        raise ValueError("%s: %s is on %s: caspr_amd kernels need tensors on the GPU, there is no CPU fallback" % (fn, name, t.device))
+
+
+class _Chamfer(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, q):
+        d1, d2, i1, i2 = ops.chamfer_distance(p, q, return_indices=True)
+        ctx.save_for_backward(p, q, i1, i2)
+        ctx.set_materialize_grads(False)        # an unused distance vector arrives as None -> a NULL pointer, not a tensor of zeros
+        return d1, d2
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g1, g2):
+        p, q, i1, i2 = ctx.saved_tensors
+        want_p, want_q = ctx.needs_input_grad
+        if g1 is None and g2 is None:
+            return None, None
+        g1 = None if g1 is None else g1.contiguous()
+        g2 = None if g2 is None else g2.contiguous()
+        return train_ops.chamfer_bwd(p, q, i1, i2, g1, g2, want_p=want_p, want_q=want_q)
+
+
+def chamfer_distance(p, q):
+    """p (F,n,3), q (F,m,3) float32 contiguous GPU tensors -> dist1 (F,n) = min_j |p_i - q_j|^2, dist2 (F,m) = min_i |p_i - q_j|^2: the bits of
+    ops.chamfer_distance, differentiable in whichever of p and q requires grad (the other's gradient is not computed).  The gradient
+    flows through the nearest neighbour only, the smallest index on ties; a point without a finite candidate has dist = +inf and
+    no gradient.  First order only: the backward is once_differentiable, a double backward raises.  The indices themselves:
+    ops.chamfer_distance(p, q, return_indices=True)."""
+    _chk_cloud("chamfer_distance", "p", p)
+    _chk_cloud("chamfer_distance", "q", q)
+    if p.shape[0] != q.shape[0]:
+        raise ValueError("chamfer_distance: p and q disagree on F: p is %s, q is %s" % (tuple(p.shape), tuple(q.shape)))
+    _chk_gpu("chamfer_distance", "p", p)
+    _chk_gpu("chamfer_distance", "q", q)
+    return _Chamfer.apply(p, q)
+
+
+def chamfer_loss(pred, gt, reduction="mean"):
+    """The Chamfer-L2 of utils.evaluations.eval_reconstr_frames (evaluations.py:36-44) as a loss: per frame
+    mean_i dist1 + mean_j dist2.  pred (F,N,3) or (B,T,N,3), gt the same with its own point count.
+    reduction: "mean" over the frames (a scalar), "sum", or "none" (the per-frame values, (F,) or (B,T))."""
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError("chamfer_loss: reduction must be 'mean', 'sum' or 'none', got %r" % (reduction,))
+    if not (torch.is_tensor(pred) and torch.is_tensor(gt)) or pred.dim() not in (3, 4) or gt.dim() != pred.dim() or pred.shape[:-2] != gt.shape[:-2]:
+        raise ValueError("chamfer_loss: pred and gt must both be (F,N,3) or (B,T,N,3) with the same leading sizes, got pred %s, gt %s"
+                         % (tuple(pred.shape) if torch.is_tensor(pred) else type(pred).__name__, tuple(gt.shape) if torch.is_tensor(gt) else type(gt).__name__))
+    lead = pred.shape[:-2]
+    for name, t in (("pred", pred), ("gt", gt)):            # before the reshape, which would silently copy a strided tensor
+        if not t.is_contiguous():
+            raise ValueError("chamfer_loss: %s must be contiguous (call .contiguous())" % name)
+    p3, g3 = pred.reshape(-1, pred.shape[-2], pred.shape[-1]), gt.reshape(-1, gt.shape[-2], gt.shape[-1])
+    _chk_cloud("chamfer_loss", "pred", p3)
+    _chk_cloud("chamfer_loss", "gt", g3)
+    _chk_gpu("chamfer_loss", "pred", p3)
+    _chk_gpu("chamfer_loss", "gt", g3)
+    d1, d2 = _Chamfer.apply(p3, g3)
+    per_frame = d1.mean(dim=1) + d2.mean(dim=1)
+    if reduction == "mean":
+        return per_frame.mean()
+    if reduction == "sum":
+        return per_frame.sum()
+    return per_frame.reshape(lead)

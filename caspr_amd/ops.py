@@ -1484,13 +1484,23 @@ def cnf_dopri5(y, hyper, tcol, w0, b0, b1, b2, w3, b3, w1x, w2x, t_end, rtol, at
     return res[0] if len(res) == 1 else res
 
 
-def chamfer_distance(p, q):
-    """tk3dv `ChamferDistance()(pred, gt)` (evaluations.py:40): -> dist1 (B,n), dist2 (B,m) squared NN distances."""
+def chamfer_distance(p, q, return_indices=False):
+    """tk3dv `ChamferDistance()(pred, gt)` (evaluations.py:40): -> dist1 (B,n), dist2 (B,m) squared NN distances.
+    return_indices: -> (dist1, dist2, idx1 (B,n), idx2 (B,m)) from caspr_chamfer_idx_f32: the same distances bit for bit and the
+    smallest index attaining each (int32; -1 with dist = +inf where no candidate is at a finite distance).  No gradient is
+    recorded here: caspr_amd.losses.chamfer_distance is the differentiable form."""
     _chk_f32(p, q)
     B, n, _ = p.shape
     m = q.shape[1]
     d1 = torch.empty(B, n, device=p.device, dtype=torch.float32)
     d2 = torch.empty(B, m, device=p.device, dtype=torch.float32)
+    if return_indices:
+        if p.dim() != 3 or q.dim() != 3 or p.shape[2] != 3 or q.shape[2] != 3 or q.shape[0] != B:
+            raise ValueError("chamfer_distance: p (F,n,3) and q (F,m,3) must agree on F, got %s and %s" % (tuple(p.shape), tuple(q.shape)))
+        i1 = torch.empty(B, n, device=p.device, dtype=torch.int32)
+        i2 = torch.empty(B, m, device=p.device, dtype=torch.int32)
+        _lib.check(_lib.load().caspr_chamfer_idx_f32(_p(p), _p(q), B, n, m, _p(d1), _p(d2), _p(i1), _p(i2), _stream()), "caspr_chamfer_idx_f32")
+        return d1, d2, i1, i2
     _lib.check(_lib.load().caspr_chamfer_f32(_p(p), _p(q), B, n, m, _p(d1), _p(d2), _stream()), "caspr_chamfer_f32")
     return d1, d2
 

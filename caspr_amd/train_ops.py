@@ -382,3 +382,24 @@ def segment_sum(src, seg, C, dst, col0=0, accumulate=True):
     _lib.check(_lib.load().caspr_segment_sum_f32(_p(src2), src2.stride(0), col0, _p(seg.start), _p(seg.row), _p(seg.w), seg.n_targets, C,
                                                  _p(dst2), dst2.stride(0), int(accumulate), _stream()), "caspr_segment_sum_f32")
     return dst
+
+
+def chamfer_bwd(p, q, idx1, idx2, g1=None, g2=None, want_p=True, want_q=True):
+    """Gradient of ops.chamfer_distance(p, q, return_indices=True)'s two distance vectors (caspr_chamfer_bwd_f32): p (B,n,3), q (B,m,3),
+    idx1 (B,n) / idx2 (B,m) int32 as returned there, g1 (B,n) / g2 (B,m) = dL/d dist1 / dL/d dist2 (None = zero).
+    -> (dp (B,n,3) | None, dq (B,m,3) | None): a gradient that is not wanted is not computed.  Fixed summation order, no atomics."""
+    _chk_f32(p, q, g1, g2)
+    _chk_i32(idx1, idx2)
+    B, n, _ = p.shape
+    m = q.shape[1]
+    if q.shape[0] != B or tuple(idx1.shape) != (B, n) or tuple(idx2.shape) != (B, m):
+        raise ValueError("chamfer_bwd: p %s, q %s, idx1 %s, idx2 %s disagree" % (tuple(p.shape), tuple(q.shape), tuple(idx1.shape), tuple(idx2.shape)))
+    if (g1 is not None and tuple(g1.shape) != (B, n)) or (g2 is not None and tuple(g2.shape) != (B, m)):
+        raise ValueError("chamfer_bwd: g1 must be (%d,%d) and g2 (%d,%d)" % (B, n, B, m))
+    if not (want_p or want_q):
+        return None, None
+    dp = torch.empty_like(p) if want_p else None
+    dq = torch.empty_like(q) if want_q else None
+    _lib.check(_lib.load().caspr_chamfer_bwd_f32(_p(p), _p(q), B, n, m, _p(idx1), _p(idx2), _p(g1), _p(g2), _p(dp), _p(dq), _stream()),
+               "caspr_chamfer_bwd_f32")
+    return dp, dq

@@ -487,6 +487,15 @@ int caspr_cnf_dopri5_h3_f32(const float *y_in, const float *hyper, int ldh, cons
 int caspr_chamfer_f32(const float *p, const float *q, int B, int n, int m, float *dist1, float *dist2,
                       void *stream);
 
+/* The same two distance vectors (bit for bit) with the nearest neighbour's index, for a loss that is differentiated: the Chamfer
+ * term the reference forms at utils/evaluations.py:40-44 (tk3dv ChamferDistance keeps the indices for its own backward).
+ * idx1 (B,n) = the smallest j attaining dist1[b,i], idx2 (B,m) = the smallest i attaining dist2[b,j] (strict < over ascending
+ * candidates).  A distance that is NaN never wins: a point with a NaN coordinate, or one facing no finite candidate, gets
+ * dist = +inf and idx = -1, and no index points at a NaN point.  Both directions in one launch; B <= 65535 (grid.y).
+ * Gradient: caspr_chamfer_bwd_f32 (caspr_hip_train.h).                                                                  */
+int caspr_chamfer_idx_f32(const float *p, const float *q, int B, int n, int m, float *dist1, float *dist2,
+                          int32_t *idx1, int32_t *idx2, void *stream);
+
 /* ---------------- approximate EMD (utils/emd.py: emd_cuda approxmatch + matchcost; call site
  * utils/evaluations.py:45) -- p (B,n,3), q (B,m,3) -> cost (B) = sum_{k,l} match[k,l] |p_k - q_l| with the
  * 10-level annealed soft assignment of approxmatch (the caller divides by n, evaluations.py:46).

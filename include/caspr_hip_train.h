@@ -95,6 +95,16 @@ int caspr_group_rows_bwd_f32(const float *dG, int ldg, const int32_t *idx, int B
 int caspr_segment_sum_f32(const float *src, int lds, int col0, const int32_t *seg_start, const int32_t *seg_row,
                           const float *seg_w, long targets, int C, float *dst, int ldd, int accumulate, void *stream);
 
+/* Chamfer backward (the autograd node of tk3dv's ChamferDistance at utils/evaluations.py:40, differentiated wherever the
+ * Chamfer term of evaluations.py:40-44 is a loss): p (B,n,3), q (B,m,3), idx1 (B,n) / idx2 (B,m) from caspr_chamfer_idx_f32,
+ * g1 (B,n) / g2 (B,m) = dL/d dist1 / dL/d dist2 (either NULL = zero).  With a = idx1[b,i]
+ *   dp[b,i] = 2 g1[b,i] (p_i - q_a) + sum_{j ascending, idx2[b,j] == i} 2 g2[b,j] (p_i - q_j)         dq: the mirror image.
+ * dp (B,n,3) / dq (B,m,3) are WRITTEN, not accumulated into; either may be NULL = not wanted (not both).  An index outside the
+ * other cloud (-1: no finite candidate) contributes nothing and nothing is read at it, its g included.  No float atomics: a
+ * thread owns one output point and adds its matches in ascending order -> bit-reproducible.  One launch; B <= 65535.       */
+int caspr_chamfer_bwd_f32(const float *p, const float *q, int B, int n, int m, const int32_t *idx1, const int32_t *idx2,
+                          const float *g1, const float *g2, float *dp, float *dq, void *stream);
+
 /* GroupNorm(16) over one neighbourhood (ns rows) at a time (PointNetFeatureExtractor, pointnet2.py:
  * 649-703).  Y (NB*ns, ldy).  Forward writes mean/rstd (NB,16) and either the dense activation
  * A = relu?(gn(Y)) or, for the last layer, maxout (NB, ldm) = max over the ns rows and arg (NB,C) =
