@@ -26,7 +26,8 @@ EXTRA = {"point_ops.hip": ["-ffp-contract=off"], "emd.hip": ["-ffp-contract=off"
 # next to the production library as libcaspr_hip_debug.so with its own objects; tools/*_phase_trace.py load it.
 DEBUG = os.environ.get("CASPR_BUILD_DEBUG", "0") not in ("0", "")
 # CASPR_XW_EXP=<bits>: a debug flavour whose 128-point CNF kernel is compiled with -DXW_EXP=<bits> (timing experiments that
-# switch parts of the kernel off at compile time, see ode_bf16x6w.hip) -> libcaspr_hip_debug_xw<bits>.so, for tools/cnf_x6w_trace.py --lib
+# switch parts of the kernel off at compile time, see ode_bf16x6w.hip; ode_f16x3w.hip has its own bits, which bring back the parent's
+# instruction stream item by item) -> libcaspr_hip_debug_xw<bits>.so, for tools/cnf_x6w_trace.py --lib and tools/cnf_h3w_trace.py --lib
 XW_EXP = os.environ.get("CASPR_XW_EXP", "")
 DEBUG = DEBUG or bool(XW_EXP)
 OUT = os.path.join(HERE, ("libcaspr_hip_debug_xw%s.so" % XW_EXP) if XW_EXP else ("libcaspr_hip_debug.so" if DEBUG else "libcaspr_hip.so"))
@@ -54,7 +55,7 @@ def build(force=False, verbose=False):
     objs, jobs, by_src = [], [], {}
     for s in SOURCES:
         src = os.path.join(HERE, s)
-        xw = XW_EXP if (XW_EXP and s in ("ode_bf16x6w.hip", "gemm_bf16x6w.hip", "gemm_f16x3w.hip")) else ""
+        xw = XW_EXP if (XW_EXP and s in ("ode_bf16x6w.hip", "ode_f16x3w.hip", "gemm_bf16x6w.hip", "gemm_f16x3w.hip")) else ""
         obj = os.path.join(HERE, s.replace(".hip", (".dbg_xw%s.o" % xw) if xw else (".dbg.o" if DEBUG else ".o")))
         objs.append(obj)
         if not xw:

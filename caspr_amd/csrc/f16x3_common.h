@@ -28,6 +28,26 @@ __device__ __forceinline__ unsigned xh_cvt_pk(float lo, float hi)
     return __builtin_bit_cast(unsigned, __builtin_convertvector(v, xh_f16x2));
 }
 
+// A plane word (two f16) with the halves whose exponent field is 0 -- subnormals and zeros -- set to +0: h * min(e, 1) per half, e the
+// half shifted right by 10 (SIGNED: after the sign bits are masked out of it; without, for words whose halves are known non-negative).
+// Exponent 31 (inf, NaN) passes.  Three / four single-pass VALU instructions for two values (v_pk_lshrrev_b16, v_pk_min_u16,
+// v_pk_mul_lo_u16).  `ones` is 0x00010001 in a register the compiler cannot see through (xh_ones): with a literal it rewrites
+// min(e, 1) as e != 0 and the product as a select, i.e. the compare per half this is here to avoid
+typedef unsigned short xh_u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned xh_ones()
+{
+    unsigned v = 0x00010001u;
+    asm volatile("" : "+v"(v));
+    return v;
+}
+template <bool SIGNED>
+__device__ __forceinline__ unsigned xh_flush_word(unsigned w, unsigned ones)
+{
+    const xh_u16x2 h = __builtin_bit_cast(xh_u16x2, w);
+    const xh_u16x2 e = __builtin_bit_cast(xh_u16x2, SIGNED ? (w & 0x7fff7fffu) : w) >> (unsigned short)10;
+    return __builtin_bit_cast(unsigned, h * __builtin_elementwise_min(e, __builtin_bit_cast(xh_u16x2, ones)));
+}
+
 // the shift s that puts max |W| 2^s in [2^14, 2^15): 14 - floor(log2 max); 0 for an all-zero, subnormal or non-finite layer.  Clamped at
 // XH_MAX_SHIFT so that the unscale factors 2^-s and 2^-(4 + s) the kernels fold into their read-out stay NORMAL f32 numbers (a gate times
 // a subnormal factor would flush and the layer would put out its bias alone): a layer whose max |W| is below 2^-86 keeps shift 100 and

@@ -8,7 +8,11 @@
 //    ring with vmcnt(24) piece barriers, the 2^4 activation scale and the weight shifts behind the pack_cnf_h3 packs, the explicit
 //    subnormal flush, v_max3_f32 range tracking.  The stage loop is `#pragma unroll 1` with ONE copy of the body: the accumulator-move
 //    and MFMA counts are those of the RK4 kernel (audit.audit_cnf_dp5_h3w).  The piece sequence keeps running across the stages of a
-//    launch (128 pieces a stage, a multiple of the ring: the last pieces of a stage prefetch the first of the next);
+//    launch (128 pieces a stage, a multiple of the ring: the last pieces of a stage prefetch the first of the next).  The INSTRUCTION
+//    STREAM has since diverged (same values, same bits): the RK4 kernel now flushes on the f16 word (xh_flush_word) and writes M0 and
+//    the source address once per piece; this copy keeps the f32 compare-and-select flush and one M0 write per LDS-DMA instruction
+//    (audit_cnf_dp5_h3w still asks for that).  Bringing both over needs this kernel's register budget rechecked (.vgpr_count 488 of
+//    512; the word flush holds one more VGPR) and was not timed;
 //  * loop: cnf_dp5_kernel<false>'s -- one launch per attempt; launch 0 evaluates f(t0, y0), launch 1 f(t0 + h0, y0 + h0 f0), launch
 //    L >= 2 decides attempt L - 3 and runs the six stages of attempt L - 2; a workgroup writes its f64 partial sums of squares to ITS slot
 //    (double-buffered by launch parity), the next launch's prologue adds a frame's slots in slot order: every workgroup of the frame

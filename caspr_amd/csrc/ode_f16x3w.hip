@@ -27,6 +27,27 @@
 //    producers run two micro-steps per slot in pass 0 of layer 2 (the same work per k-step under half the MFMAs).
 #include "f16x3_common.h"
 
+// XW_EXP (debug flavours only, build.py CASPR_XW_EXP): 16 = no phase stamps; 65536 / 131072 = the instruction stream of the parent for
+// ONE item of "the wave's instruction stream" (DESIGN.md 3): the f32 compare-and-select flush, an address and an M0 write per LDS-DMA
+// instruction.  Same output bits with either set.  1048576 / 2097152 = NO flush of plane 1 / plane 2 (WRONG results where a plane
+// value is an f16 subnormal: what tests/test_cnf_f16x3_flush_band.py must notice).
+#ifndef XW_EXP
+#define XW_EXP 0
+#endif
+#define XH_OLD_FLUSH ((XW_EXP & 65536) != 0)
+#define XH_OLD_DMA ((XW_EXP & 131072) != 0)
+#define XH_NO_FLUSH1 ((XW_EXP & 1048576) != 0)
+#define XH_NO_FLUSH2 ((XW_EXP & 2097152) != 0)
+// debug build (tools/cnf_h3w_trace.py): s_memtime stamps of workgroup (0,0), thread 0, RK4 step 0, sixteen slots per stage: 0 stage head,
+// 1 tables built, 2 chunk 0 of the input layer done, 3 layer 1 done, 4 + 2 q the K loop of pass q done, 5 + 2 q its epilogue, 12 stage end.
+// The stamped kernel does NOT fit its registers (115 VGPRs spilled with the tested compiler, as the bf16x6 kernel's stamped flavour spills
+// 134): its scratch traffic shares vmcnt with the weight ring, so the split is indicative and a stamped stage is far slower than a real one
+#if defined(CASPR_DEBUG_HOOKS) && !(XW_EXP & 16)
+#define XH_STAMP(i) if (a.trace && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0 && step == 0) a.trace[16 * stage + (i)] = __builtin_amdgcn_s_memtime();
+#else
+#define XH_STAMP(i)
+#endif
+
 #define XH_PTS 128
 #define XH_FRAG 1024                      // one A fragment of v_mfma_f32_32x32x16_f16: 64 lanes x 16 B
 #define XH_PIECE (2 * 4 * 2 * XH_FRAG)    // 16 KB: [k-step 2][row tile 4][plane 2][fragment]
@@ -54,19 +75,34 @@ __device__ __forceinline__ void xh_sp3(XwPair &p, float &xmax)     // X = max(X,
     // (as asm: left to hipcc, the maxima are re-associated and sunk to the end of the stage, every X of the stage kept live for them)
     asm volatile("v_max3_f32 %0, %0, %1, %2" : "+v"(xmax) : "v"(p.x0), "v"(p.x1));
 }
-__device__ __forceinline__ void xh_split1(XwPair &p)  // first plane (flushed) + remainder; X >= 0 here
+// The flush is done on the f16 WORD: x < XH_FLUSH holds exactly when rne16(x) has exponent field 0, so zeroing such a half after the
+// conversion (xh_flush_word: packed 16-bit integer operations, no compare, no select, no VCC) gives the plane word that flushing the
+// f32 value in front of it gave.  The remainder is taken from the unflushed X: for a flushed half it is X itself, below 2^-14, which
+// the second plane's flush zeroes (to +0, whatever its sign) -- tests/test_f16x3_flush_word.py restates both forms on the CPU
+__device__ __forceinline__ void xh_split1(XwPair &p, unsigned ones)  // first plane (flushed) + remainder; X >= 0 here
 {
-    const float a0 = p.x0 < XH_FLUSH ? 0.0f : p.x0, a1 = p.x1 < XH_FLUSH ? 0.0f : p.x1;
-    p.p1 = xh_cvt_pk(a0, a1);
-    const xh_f16x2 hv = __builtin_bit_cast(xh_f16x2, p.p1);
-    p.r0 = a0 - (float)hv[0];
-    p.r1 = a1 - (float)hv[1];
+    if constexpr (XH_OLD_FLUSH) {
+        const float a0 = p.x0 < XH_FLUSH ? 0.0f : p.x0, a1 = p.x1 < XH_FLUSH ? 0.0f : p.x1;
+        p.p1 = xh_cvt_pk(a0, a1);
+        const xh_f16x2 hv = __builtin_bit_cast(xh_f16x2, p.p1);
+        p.r0 = a0 - (float)hv[0];
+        p.r1 = a1 - (float)hv[1];
+    } else {
+        p.p1 = XH_NO_FLUSH1 ? xh_cvt_pk(p.x0, p.x1) : xh_flush_word<false>(xh_cvt_pk(p.x0, p.x1), ones);
+        const xh_f16x2 hv = __builtin_bit_cast(xh_f16x2, p.p1);
+        p.r0 = p.x0 - (float)hv[0];
+        p.r1 = p.x1 - (float)hv[1];
+    }
 }
-__device__ __forceinline__ void xh_split2(XwPair &p, u32x4 (&bw)[2], int q)
+__device__ __forceinline__ void xh_split2(XwPair &p, u32x4 (&bw)[2], int q, unsigned ones)
 {
-    const float r0 = fabsf(p.r0) < XH_FLUSH ? 0.0f : p.r0, r1 = fabsf(p.r1) < XH_FLUSH ? 0.0f : p.r1;
     bw[0][q] = p.p1;
-    bw[1][q] = xh_cvt_pk(r0, r1);
+    if constexpr (XH_OLD_FLUSH) {
+        const float r0 = fabsf(p.r0) < XH_FLUSH ? 0.0f : p.r0, r1 = fabsf(p.r1) < XH_FLUSH ? 0.0f : p.r1;
+        bw[1][q] = xh_cvt_pk(r0, r1);
+    } else {
+        bw[1][q] = XH_NO_FLUSH2 ? xh_cvt_pk(p.r0, p.r1) : xh_flush_word<true>(xh_cvt_pk(p.r0, p.r1), ones);
+    }
 }
 // a plane word (two f16) in / out of the accumulator file, bits untouched
 template <int N>
@@ -155,21 +191,41 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
         const unsigned dst = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)(wbuf + (s_ & (XH_RING - 1)) * XH_PIECE + (wave * 4 + i0) * 1024);
         asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(dst), "v"(lane16), "s"(src) : "memory");
     };
+    // ... and the four of a piece on ONE source address and ONE M0 write: kilobyte i0 is 1024 i0 further on both sides, which is
+    // what the instruction's immediate offset adds to the global AND to the LDS address.  dma_open (the wave's share of piece s_:
+    // M0 <- its place in the ring, returns its place in the pack) goes into the slot in front of the first dma_kb, so that an MFMA
+    // supplies the wait state between the M0 write and the load; M0 then stays put until the next piece's dma_open
+    auto dma_open = [&](int s_) XW_INL -> const unsigned char * {
+        const unsigned dst = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)(wbuf + (s_ & (XH_RING - 1)) * XH_PIECE + wave * 4096);
+        asm volatile("s_mov_b32 m0, %0" : : "s"(dst) : "memory");
+        return piece_src(s_) + wave * 4096;
+    };
+    auto dma_kb = [&](const unsigned char *src, int lane16, auto I0) XW_INL {
+        asm volatile("global_load_lds_dwordx4 %0, %1 offset:%c2" : : "v"(lane16), "s"(src), "i"(1024 * decltype(I0)::value) : "memory");
+    };
     const double t0 = a.reverse ? (double)a.t_end : 0.0, t1 = a.reverse ? 0.0 : (double)a.t_end;
     const double h = (t1 - t0) / (double)S;
     const float hh = (float)h, h2 = (float)(0.5 * h), h6 = (float)(h / 6.0);
 
     // pieces 0..6 in flight before the first one is consumed
 #pragma unroll
-    for (int s_ = 0; s_ < XH_RING - 1; ++s_)
+    for (int s_ = 0; s_ < XH_RING - 1; ++s_) {
+        if constexpr (XH_OLD_DMA) {
 #pragma unroll
-        for (int i0 = 0; i0 < 4; ++i0) dma1(s_, lane0 * 16, i0);
+            for (int i0 = 0; i0 < 4; ++i0) dma1(s_, lane0 * 16, i0);
+        } else {
+            const unsigned char *src = dma_open(s_);
+            asm volatile("s_nop 0" ::: "memory");      // M0 write -> LDS-DMA: one wait state (no MFMA in between here)
+            xw_for<0, 4>([&](auto I0) XW_INL { dma_kb(src, lane0 * 16, I0); });
+        }
+    }
 
     f32x16 acc2[4];               // layer 2: the 128 rows of the running pass
     f16x8 fX[2][2], fY[2][2];     // A fragments: two sets of two row tiles x two planes
     u32x4 b1w[2][2][2];           // layer 1 B planes [chunk parity][k-step of the chunk][plane]
     u32x4 b2w[2][2];              // layer 2 B planes [k-step parity][plane]
     float xmax = 0.0f;            // range guard: the largest scaled activation this lane has split
+    const unsigned ones = xh_ones();   // for the flush of the plane words
 
     // fragments of region 0 of piece 0 (k-step 0, row tiles 0, 1): the only exposed fragment read of the kernel
     asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
@@ -193,8 +249,11 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
             asm volatile("" : "+v"(lane));     // opaque: nothing derived from the lane id is hoisted out of the stage loop
             const int hq = (lane >> 5) * 4, lane16 = lane * 16;
             // layer 1 accumulates from zero (issued before the barrier: overlaps the other waves' arrival)
+            XH_STAMP(0)
             xw_for<0, 256>([&](auto N) XW_INL { xw_acc_zero<decltype(N)::value>(); });
             __syncthreads();   // the previous stage's epilogues are done with the tables
+            // (RK4 stages 1 and 2 both sit at t + h / 2 and build the same tables; skipping the second build and its barrier was measured and
+            // is not worth a branch here: the launch is as fast with it)
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const int i = tid + 256 * u;
@@ -216,6 +275,7 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
                 s_g3[4 + tid] = fmaf(k3_b, gt, fmaf(t, k3_tb, k3_hb));
             }
             __syncthreads();
+            XH_STAMP(1)
 
             float ys[3];
 #pragma unroll
@@ -314,8 +374,8 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
                 if constexpr (i == 1) xh_sp1(pa);
                 if constexpr (i == 2) xw_sp2(pa);
                 if constexpr (i == 3) xh_sp3(pa, xmax);
-                if constexpr (i == 4) xh_split1(pa);
-                if constexpr (i == 5) xh_split2(pa, bw, 2 * grp + pr);
+                if constexpr (i == 4) xh_split1(pa, ones);
+                if constexpr (i == 5) xh_split2(pa, bw, 2 * grp + pr, ones);
             };
             // chunk 0 of the input layer up front (exposed: 1/16 of the input layer)
 #pragma unroll
@@ -329,11 +389,12 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
                         xh_sp1(pa);
                         xw_sp2(pa);
                         xh_sp3(pa, xmax);
-                        xh_split1(pa);
-                        xh_split2(pa, b1w[0][ks], 2 * grp + pr);
+                        xh_split1(pa, ones);
+                        xh_split2(pa, b1w[0][ks], 2 * grp + pr, ones);
                     }
                 }
             XW_FENCE;
+            XH_STAMP(2)
 #pragma unroll 1
             for (int it = 0; it < 8; ++it) {
                 xw_for<0, 8>([&](auto PC) XW_INL {
@@ -343,35 +404,44 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
                     const unsigned char *An = wbuf + ((pc + 1) & (XH_RING - 1)) * XH_PIECE + lane16;
                     // producers of chunk kc + 1 (B set par ^ 1): piece rq makes group (ks = rq >> 1, grp = rq & 1): tables in
                     // region 0, one pair in regions 1 and 2 each.  (Chunk 16 does not exist: the last pass produces chunk 0 once
-                    // more -- values the range guard has already seen -- into a B set nobody multiplies.)
+                    // more -- values the range guard has already seen -- into a B set nobody multiplies.  Skipping it takes a uniform
+                    // branch in each of the 13 producer slots of pieces 4-7: hipcc turns those into more instructions in the seven
+                    // passes that produce than the eighth saves)
                     const int ubn = 32 * ((2 * it + par + 1) & 15) + 16 * (rq >> 1) + 8 * (rq & 1) + hq;
                     u32x4 (&bn)[2] = b1w[par ^ 1][rq >> 1];
+                    const unsigned char *dsrc = nullptr;     // this wave's share of piece s1 + 7 in the pack (dma_open)
+                    auto dma = [&](auto I0) XW_INL {
+                        if constexpr (XH_OLD_DMA) dma1(s1 + 7, lane16, decltype(I0)::value);
+                        else dma_kb(dsrc, lane16, I0);
+                    };
                     // region 0: k-step 0, row tiles 0, 1 (fX) | reads k-step 0, row tiles 2, 3 -> fY
                     region_a(std::integral_constant<int, 4 * rq>{}, fX, b1w[par][0], fY, A + 4 * XH_FRAG, [&](auto I) XW_INL {
                         constexpr int i = decltype(I)::value;
                         if constexpr (i == 0) l1_tab(ubn);
-                        if constexpr (i == 4) dma1(s1 + 7, lane16, 0);
+                        if constexpr (i == 3 && !XH_OLD_DMA) dsrc = dma_open(s1 + 7);
+                        if constexpr (i == 4) dma(std::integral_constant<int, 0>{});
                     });
                     // region 1: k-step 0, row tiles 2, 3 (fY) | reads k-step 1, row tiles 0, 1 -> fX
                     region_a(std::integral_constant<int, 4 * rq + 2>{}, fY, b1w[par][0], fX, A + 8 * XH_FRAG, [&](auto I) XW_INL {
                         constexpr int i = decltype(I)::value;
                         l1_pair_step(I, bn, rq & 1, 0);
-                        if constexpr (i == 3) dma1(s1 + 7, lane16, 1);
+                        if constexpr (i == 3) dma(std::integral_constant<int, 1>{});
                     });
                     // region 2: k-step 1, row tiles 0, 1 (fX) | reads k-step 1, row tiles 2, 3 -> fY
                     region_a(std::integral_constant<int, 4 * rq>{}, fX, b1w[par][1], fY, A + 12 * XH_FRAG, [&](auto I) XW_INL {
                         constexpr int i = decltype(I)::value;
                         l1_pair_step(I, bn, rq & 1, 1);
-                        if constexpr (i == 3) dma1(s1 + 7, lane16, 2);
+                        if constexpr (i == 3) dma(std::integral_constant<int, 2>{});
                     });
                     // region 3: the last kilobyte of piece s1 + 7 | barrier of the next piece | k-step 1, row tiles 2, 3 (fY) | reads
                     // the next piece's k-step 0, row tiles 0, 1 -> fX
                     region_a_last(std::integral_constant<int, 4 * rq + 2>{}, fY, b1w[par][1], fX, An, [&](auto I) XW_INL {
                         constexpr int i = decltype(I)::value;
-                        if constexpr (i == 1) dma1(s1 + 7, lane16, 3);
+                        if constexpr (i == 1) dma(std::integral_constant<int, 3>{});
                     });
                 });
             }
+            XH_STAMP(3)
 
             // ================= layer 2: four passes of 16 pieces, sequence pieces 64 + 16 q + kc =================
             float part[3] = {0.f, 0.f, 0.f};
@@ -414,12 +484,12 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
                         xh_sp3(pb, xmax);
                     }
                     if constexpr (i == 4) {
-                        xh_split1(pa);
-                        xh_split1(pb);
+                        xh_split1(pa, ones);
+                        xh_split1(pb, ones);
                     }
                     if constexpr (i == 5) {
-                        xh_split2(pa, bw, 2 * grp);
-                        xh_split2(pb, bw, 2 * grp + 1);
+                        xh_split2(pa, bw, 2 * grp, ones);
+                        xh_split2(pb, bw, 2 * grp + 1, ones);
                         xh_acc_wr_u<base>(bw[0][2 * grp]);
                         xh_acc_wr_u<base + 1>(bw[1][2 * grp]);
                         xh_acc_wr_u<base + 2>(bw[0][2 * grp + 1]);
@@ -458,6 +528,11 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
                     const unsigned char *A = wbuf + (kc & (XH_RING - 1)) * XH_PIECE + lane16;            // sq & 7 == kc & 7
                     const unsigned char *An = wbuf + ((kc + 1) & (XH_RING - 1)) * XH_PIECE + lane16;
                     constexpr int tb = 2 * kc + 1, tn = (kc < 15 ? 2 * kc + 2 : 0);
+                    const unsigned char *dsrc = nullptr;     // this wave's share of piece sq + 7 in the pack (dma_open)
+                    auto dma = [&](auto I0) XW_INL {
+                        if constexpr (XH_OLD_DMA) dma1(sq + 7, lane16, decltype(I0)::value);
+                        else dma_kb(dsrc, lane16, I0);
+                    };
                     // k-step t + 1 is produced during k-step t: group 0 in the region of row tiles 0, 1 (tables in tt[0]), group 1 in
                     // the region of row tiles 2, 3 (tt[1]); slot 3 of a region reads the tables of the next region's group
                     // region 0: k-step 2 kc, row tiles 0, 1 (fX) | reads row tiles 2, 3 -> fY | group 0 of k-step tb
@@ -465,21 +540,22 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
                         constexpr int i = decltype(I)::value;
                         l2_step(I, std::integral_constant<int, tb>{}, std::integral_constant<int, 0>{}, FC, b2w[1], 0);
                         if constexpr (first && i == 3) l2_tab(1, tb, 1);
-                        if constexpr (i == 4) dma1(sq + 7, lane16, 0);
+                        if constexpr (i == 3 && !XH_OLD_DMA) dsrc = dma_open(sq + 7);
+                        if constexpr (i == 4) dma(std::integral_constant<int, 0>{});
                     });
                     // region 1: k-step 2 kc, row tiles 2, 3 (fY) | reads tb, row tiles 0, 1 -> fX | group 1 of tb
                     region_v(acc2[2], acc2[3], fY, b2w[0], fX, A + 8 * XH_FRAG, [&](auto I) XW_INL {
                         constexpr int i = decltype(I)::value;
                         l2_step(I, std::integral_constant<int, tb>{}, std::integral_constant<int, 1>{}, FC, b2w[1], 1);
                         if constexpr (first && kc < 15 && i == 3) l2_tab(0, tn, 0);
-                        if constexpr (i == 4) dma1(sq + 7, lane16, 1);
+                        if constexpr (i == 4) dma(std::integral_constant<int, 1>{});
                     });
                     // region 2: k-step tb, row tiles 0, 1 (fX) | reads tb, row tiles 2, 3 -> fY | group 0 of k-step tb + 1
                     region_v(acc2[0], acc2[1], fX, b2w[1], fY, A + 12 * XH_FRAG, [&](auto I) XW_INL {
                         constexpr int i = decltype(I)::value;
                         if constexpr (kc < 15) l2_step(I, std::integral_constant<int, tn>{}, std::integral_constant<int, 0>{}, FC, b2w[0], 0);
                         if constexpr (first && kc < 15 && i == 3) l2_tab(1, tn, 1);
-                        if constexpr (i == 4) dma1(sq + 7, lane16, 2);
+                        if constexpr (i == 4) dma(std::integral_constant<int, 2>{});
                     });
                     // region 3: the last kilobyte of piece sq + 7 | barrier of the next piece | k-step tb, row tiles 2, 3 (fY) | reads
                     // the next piece's first fragments -> fX | group 1 of k-step tb + 1
@@ -487,9 +563,10 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
                         constexpr int i = decltype(I)::value;
                         if constexpr (kc < 15) l2_step(I, std::integral_constant<int, tn>{}, std::integral_constant<int, 1>{}, FC, b2w[0], 1);
                         if constexpr (first && kc < 15 && i == 3) l2_tab(0, tn + 1, 0);
-                        if constexpr (i == 1) dma1(sq + 7, lane16, 3);
+                        if constexpr (i == 1) dma(std::integral_constant<int, 3>{});
                     });
                 });
+                XH_STAMP(4 + 2 * q)
                 // ---- epilogue of hidden layer 2 for rows 128 q .. 128 q + 127 + their share of the 512 -> 3 output layer:
                 // acc2[rt] register r <-> unit 128 q + 32 rt + 8 (r >> 2) + 4 h + (r & 3); s_g2 carries the unscale 2^-(4 + s2)
                 int le = lane;   // opaque again: the table addresses must not be hoisted above the product loop
@@ -511,6 +588,7 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
                         }
                     }
                 XW_FENCE;
+                XH_STAMP(5 + 2 * q)
             };
             int q0 = 0;
             asm volatile("" : "+s"(q0));     // opaque: the piece addresses of pass 0 are computed like those of passes 1-3 (SALU)
@@ -527,6 +605,7 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
                 kprev[d] = od;
                 kacc[d] = (stage == 0) ? od : ((stage == 3) ? kacc[d] + od : kacc[d] + 2.0f * od);
             }
+            XH_STAMP(12)
         }
 #pragma unroll
         for (int d = 0; d < 3; ++d) y[d] = y[d] + h6 * kacc[d];
@@ -612,6 +691,12 @@ extern "C" int caspr_pack_weight_cnf_h3(const float *w, int ldw, void *packed, v
     return CASPR_OK;
 }
 
+#ifdef CASPR_DEBUG_HOOKS
+static unsigned long long *g_h3_trace = nullptr;
+// 64 words; see XH_STAMP
+extern "C" void caspr_debug_set_h3_trace(unsigned long long *dev_buf) { g_h3_trace = dev_buf; }
+#endif
+
 // steps_tab / max_steps / order: the per-frame table of caspr_cnf_rk4_h3_frames_f32, NULL / 0 / NULL from the plain entry
 static int cnf_rk4_h3_run(const float *y_in, const float *hyper, int ldh, const float *tcol, const float *w0,
                           const float *b0, const void *w1h, const float *b1, const void *w2h, const float *b2,
@@ -628,6 +713,7 @@ static int cnf_rk4_h3_run(const float *y_in, const float *hyper, int ldh, const 
     a.y_in = y_in; a.hyper = hyper; a.tcol = tcol; a.w0 = w0; a.b0 = b0; a.b1 = b1; a.b2 = b2; a.w3 = w3; a.b3 = b3;
     a.mbn_in = mbn_in; a.mbn_out = mbn_out; a.w1x = (const unsigned char *)w1h; a.w2x = (const unsigned char *)w2h;
     a.e = nullptr; a.logp_in = nullptr; a.logp_out = nullptr; a.trace = nullptr; a.diag = 0;
+    CASPR_IF_DEBUG(a.trace = g_h3_trace;)
     a.y_out = y_out; a.ldh = ldh; a.n = n; a.steps = steps; a.reverse = reverse & 1; a.t_end = t_end;
     a.status = status;
     a.steps_tab = steps_tab; a.max_steps = max_steps; a.order = order;
