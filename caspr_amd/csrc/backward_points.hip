@@ -641,3 +641,92 @@ extern "C" int caspr_chamfer_bwd_f32(const float *p, const float *q, int B, int 
     CASPR_CHECK_LAUNCH("chamfer_bwd");
     return CASPR_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Approximate-EMD backward (the autograd node of utils/emd.py:17-21: emd_cuda.matchcost_backward on the saved match matrix; the
+// match is held fixed, there is no gradient through approxmatch):
+//   match[k,l] = sum_i expf(level_i |p_k - q_l|^2) ratioL_i[k] ratioR_i[l]                   level_i = -4^(7-i), 0 for i = 9
+//   d1[k] =  g sum_l match[k,l] (p_k - q_l) / sqrtf(fmaxf(|p_k - q_l|^2, 1e-20f))            d2[l] = -g sum_k (the same term)
+// The match matrix is never read: emd_kernel<true> (emd.hip) left the ten ratio vectors of every cloud pair on the tape, and every
+// entry is rebuilt here as the forward priced it -- the squared distance without contraction, (expf(level d2) * ratioL) * ratioR,
+// pass 3's association -- and summed over the levels in ascending order.  A thread owns ONE output point, keeps its ten own ratios in
+// registers and walks the other cloud in index order through LDS tiles of 16 floats per point (x y z, ten ratios, three unused; every
+// lane reads the same address: a broadcast); no float atomics -> bit-reproducible.  A coincident pair has a zero difference and
+// a finite weight (match / 1e-10): it contributes exactly 0.  One launch: blocks [0, nb1) of grid.x write d1, the rest d2.
+// ---------------------------------------------------------------------------------------------
+#define EMD_BWD_TILE 256
+#define EMD_LEVELS 10
+
+template <bool SECOND>
+__device__ __forceinline__ void emd_bwd_side(const float *__restrict__ own, const float *__restrict__ oth, int no, int nx,
+                                             const float *__restrict__ tape_own, const float *__restrict__ tape_oth, int stride, float gb,
+                                             int blk, float *__restrict__ out, float *sm)
+{
+#pragma clang fp contract(off)
+    // -4^j, j = 7 .. -1, and 0: powers of two, the values the forward's -powf(4.0f, j) takes
+    const float level[EMD_LEVELS] = {-16384.0f, -4096.0f, -1024.0f, -256.0f, -64.0f, -16.0f, -4.0f, -1.0f, -0.25f, 0.0f};
+    const long i = (long)blk * 256 + threadIdx.x;
+    const bool live = i < no;
+    float x = 0.f, y = 0.f, z = 0.f, ro[EMD_LEVELS];
+#pragma unroll
+    for (int v = 0; v < EMD_LEVELS; ++v) ro[v] = 0.f;
+    if (live) {
+        x = own[i * 3]; y = own[i * 3 + 1]; z = own[i * 3 + 2];
+#pragma unroll
+        for (int v = 0; v < EMD_LEVELS; ++v) ro[v] = tape_own[(long)v * stride + i];
+    }
+    float ax = 0.f, ay = 0.f, az = 0.f;
+    for (int base = 0; base < nx; base += EMD_BWD_TILE) {
+        const int cnt = (nx - base) < EMD_BWD_TILE ? (nx - base) : EMD_BWD_TILE;
+        __syncthreads();
+        if ((int)threadIdx.x < cnt) {
+            const long t = base + threadIdx.x;
+            float *e = sm + threadIdx.x * 16;
+            e[0] = oth[t * 3]; e[1] = oth[t * 3 + 1]; e[2] = oth[t * 3 + 2];
+#pragma unroll
+            for (int v = 0; v < EMD_LEVELS; ++v) e[3 + v] = tape_oth[(long)v * stride + t];
+        }
+        __syncthreads();
+        for (int l = 0; l < cnt; ++l) {
+            const float *e = sm + l * 16;
+            const float dx = x - e[0], dy = y - e[1], dz = z - e[2];
+            const float d2 = dx * dx + dy * dy + dz * dz;
+            float match = 0.f;
+#pragma unroll
+            for (int v = 0; v < EMD_LEVELS; ++v) {
+                const float rl = SECOND ? e[3 + v] : ro[v], rr = SECOND ? ro[v] : e[3 + v];
+                match += expf(level[v] * d2) * rl * rr;
+            }
+            const float w = match / sqrtf(fmaxf(d2, 1e-20f));
+            ax += w * dx; ay += w * dy; az += w * dz;
+        }
+    }
+    if (live) { out[i * 3] = gb * ax; out[i * 3 + 1] = gb * ay; out[i * 3 + 2] = gb * az; }
+}
+
+__global__ __launch_bounds__(256) void emd_bwd_kernel(const float *__restrict__ xyz1, const float *__restrict__ xyz2, int n, int m,
+                                                      const float *__restrict__ tape, const float *__restrict__ g, int nb1,
+                                                      float *__restrict__ d1, float *__restrict__ d2)
+{
+    __shared__ __attribute__((aligned(16))) float sm[EMD_BWD_TILE * 16];
+    const int b = blockIdx.y;
+    const float *p = xyz1 + (long)b * n * 3, *q = xyz2 + (long)b * m * 3;
+    const float *tl = tape + (long)b * EMD_LEVELS * (n + m), *tr = tl + n;   // level v: ratioL at tl[v (n + m) + k], ratioR at tr[v (n + m) + l]
+    const float gb = g[b];
+    if ((int)blockIdx.x < nb1)
+        emd_bwd_side<false>(p, q, n, m, tl, tr, n + m, gb, (int)blockIdx.x, d1 + (long)b * n * 3, sm);
+    else
+        emd_bwd_side<true>(q, p, m, n, tr, tl, n + m, gb, (int)blockIdx.x - nb1, d2 + (long)b * m * 3, sm);
+}
+
+extern "C" int caspr_emd_bwd_f32(const float *xyz1, const float *xyz2, int B, int n, int m, const float *tape, const float *g,
+                                 float *d1, float *d2, void *stream)
+{
+    CASPR_REQUIRE(xyz1 && xyz2 && tape && g && B > 0 && n > 0 && m > 0, "emd_bwd: bad arguments");
+    CASPR_REQUIRE(B <= 65535, "emd_bwd: B=%d: the cloud index is grid.y, B <= 65535", B);
+    CASPR_REQUIRE(d1 || d2, "emd_bwd: d1 and d2 are both NULL: nothing to compute");
+    const int nb1 = d1 ? ceil_div(n, 256) : 0, nb2 = d2 ? ceil_div(m, 256) : 0;
+    emd_bwd_kernel<<<dim3(nb1 + nb2, B), dim3(256), 0, (hipStream_t)stream>>>(xyz1, xyz2, n, m, tape, g, nb1, d1, d2);
+    CASPR_CHECK_LAUNCH("emd_bwd");
+    return CASPR_OK;
+}

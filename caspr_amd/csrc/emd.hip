@@ -10,12 +10,17 @@
 // and cost = sum_{k,l} match[k,l] * |p_k - q_l|.  The match matrix (n*m floats per cloud pair, 2.7 GB at cfg-2) is
 // never stored: the cost is linear in it, so every increment is priced as it is produced.
 // One workgroup per cloud pair (the levels are a serial chain), the other cloud tiled through LDS.
+//
+// The match matrix is determined by the 10 (n + m) ratio values of a cloud pair: emd_kernel<true> keeps them (level i = 7 - j writes
+// its ratioL, ratioR into tape[b][i][0 .. n + m) instead of the workspace; same arithmetic, same order, the same cost bits), and
+// caspr_emd_bwd_f32 (backward_points.hip) rebuilds every entry from them for the gradient of the cost.
 #include "common.h"
 
 #define EMD_TILE 1024
 
+template <bool TAPE>
 __global__ __launch_bounds__(256) void emd_kernel(const float *__restrict__ xyz1, const float *__restrict__ xyz2, int n, int m,
-                                                  float *__restrict__ cost, float *__restrict__ ws)
+                                                  float *__restrict__ cost, float *__restrict__ ws, float *__restrict__ tape)
 {
     __shared__ float buf[EMD_TILE * 4];
     __shared__ float red[256];
@@ -29,6 +34,7 @@ __global__ __launch_bounds__(256) void emd_kernel(const float *__restrict__ xyz1
     __syncthreads();
     for (int j = 7; j >= -2; --j) {
         const float level = j == -2 ? 0.0f : -powf(4.0f, (float)j);
+        if (TAPE) { ratioL = tape + ((long)i * 10 + (7 - j)) * (n + m); ratioR = ratioL + n; }
         // pass 1: ratioL
         for (int k0 = 0; k0 < n; k0 += 256) {
             const int k = k0 + tid;
@@ -123,7 +129,19 @@ extern "C" int caspr_emd_f32(const float *xyz1, const float *xyz2, int B, int n,
 {
     CASPR_REQUIRE(xyz1 && xyz2 && cost && ws && B > 0 && n > 0 && m > 0, "emd: bad arguments");
     CASPR_REQUIRE(ws_bytes >= caspr_emd_ws_bytes(B, n, m), "emd: workspace too small");
-    emd_kernel<<<dim3(B), dim3(256), 0, (hipStream_t)stream>>>(xyz1, xyz2, n, m, cost, (float *)ws);
+    emd_kernel<false><<<dim3(B), dim3(256), 0, (hipStream_t)stream>>>(xyz1, xyz2, n, m, cost, (float *)ws, nullptr);
     CASPR_CHECK_LAUNCH("emd");
+    return CASPR_OK;
+}
+
+extern "C" long caspr_emd_tape_bytes(int B, int n, int m) { return (long)B * 10 * (n + m) * 4; }
+
+extern "C" int caspr_emd_tape_f32(const float *xyz1, const float *xyz2, int B, int n, int m, float *cost, float *tape, void *ws,
+                                  long ws_bytes, void *stream)
+{
+    CASPR_REQUIRE(xyz1 && xyz2 && cost && tape && ws && B > 0 && n > 0 && m > 0, "emd_tape: bad arguments");
+    CASPR_REQUIRE(ws_bytes >= caspr_emd_ws_bytes(B, n, m), "emd_tape: workspace too small");
+    emd_kernel<true><<<dim3(B), dim3(256), 0, (hipStream_t)stream>>>(xyz1, xyz2, n, m, cost, (float *)ws, tape);
+    CASPR_CHECK_LAUNCH("emd_tape");
     return CASPR_OK;
 }

@@ -1,12 +1,16 @@
-"""Losses on sampled point clouds with hand-written gradients (include/caspr_hip.h: caspr_chamfer_idx_f32; include/caspr_hip_train.h:
-caspr_chamfer_bwd_f32).
+"""Losses on sampled point clouds with hand-written gradients (include/caspr_hip.h: caspr_chamfer_idx_f32, caspr_emd_tape_f32;
+include/caspr_hip_train.h: caspr_chamfer_bwd_f32, caspr_emd_bwd_f32).
 
 The reference evaluates reconstructions with the Chamfer term of utils/evaluations.py:36-44 (tk3dv ChamferDistance, which carries its
 own CUDA backward).  Here the same term is a differentiable loss on the samples of decode(differentiable=True) /
 reconstruct(differentiable=True): auto-decoding (utils/fit.py), fine-tuning the flow on its samples.  The forward keeps the two
 nearest-neighbour index vectors (4 bytes per point), never an (n, m) matrix; the backward gathers in a fixed order without float
-atomics, so gradients are bit-reproducible.  The approximate EMD (ops.earth_mover_distance) has NO gradient: emd.hip never stores the
-match matrix its gradient would need.  Same rules as ops.py: float32 contiguous GPU tensors, no CPU fallback.
+atomics, so gradients are bit-reproducible.
+
+The approximate EMD of evaluations.py:45-46 (utils/emd.py: an autograd function that saves the (n, m) match matrix) is differentiable the
+same way: its forward keeps the ten levels' ratio vectors (40 (n + m) bytes per frame), from which the backward rebuilds every entry of the
+match matrix on the fly -- the published matchcost gradient with the match held fixed, nothing through approxmatch -- again without float
+atomics.  Same rules as ops.py: float32 contiguous GPU tensors, no CPU fallback.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -15,11 +19,13 @@ from . import ops
 from . import train_ops
 
 
-def _chk_cloud(fn, name, t):
+def _chk_cloud(fn, name, t, channels_first=False):
     """`name` = the argument as the caller wrote it: every refusal says which tensor it is about.  Shape, type and layout first, the
-    device last (_chk_gpu), so that what is wrong with a tensor is reported wherever it lives."""
-    if not torch.is_tensor(t) or t.dim() != 3 or t.shape[2] != 3:
-        raise ValueError("%s: %s must be a (F,N,3) tensor, got %s" % (fn, name, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+    device last (_chk_gpu), so that what is wrong with a tensor is reported wherever it lives.  channels_first: (F,3,N), the layout
+    utils/emd.py takes with transpose=True."""
+    if not torch.is_tensor(t) or t.dim() != 3 or t.shape[1 if channels_first else 2] != 3:
+        raise ValueError("%s: %s must be a %s tensor, got %s" % (fn, name, "(F,3,N)" if channels_first else "(F,N,3)",
+                                                                 tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
     if t.dtype != torch.float32:
         raise ValueError("%s: %s must be float32, got %s" % (fn, name, t.dtype))
     if not t.is_contiguous():
@@ -86,6 +92,73 @@ def chamfer_loss(pred, gt, reduction="mean"):
     _chk_gpu("chamfer_loss", "gt", g3)
     d1, d2 = _Chamfer.apply(p3, g3)
     per_frame = d1.mean(dim=1) + d2.mean(dim=1)
+    if reduction == "mean":
+        return per_frame.mean()
+    if reduction == "sum":
+        return per_frame.sum()
+    return per_frame.reshape(lead)
+
+
+class _EMD(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, q):
+        p, q = p.contiguous(), q.contiguous()   # emd.py:8-9: the (F,N,3) view of a (F,3,N) input is copied here, as the reference does
+        cost, tape = ops.earth_mover_distance(p, q, transpose=False, return_tape=True)
+        ctx.save_for_backward(p, q, tape)
+        ctx.set_materialize_grads(False)        # an unused cost arrives as None: nothing is launched for it
+        return cost
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        p, q, tape = ctx.saved_tensors
+        want_p, want_q = ctx.needs_input_grad
+        if g is None:
+            return None, None
+        return train_ops.emd_bwd(p, q, tape, g.contiguous(), want_p=want_p, want_q=want_q)
+
+
+def earth_mover_distance(xyz1, xyz2, transpose=True):
+    """utils.emd.earth_mover_distance (emd.py:24-45) with its signature and layouts: xyz1 (F,3,n), xyz2 (F,3,m) when `transpose` (as the
+    reference calls it), else (F,n,3), (F,m,3); a 2-D cloud is one frame.  float32 contiguous GPU tensors -> cost (F,), the bits of
+    ops.earth_mover_distance, differentiable in whichever input requires grad (the other's gradient is not computed).  The gradient is
+    emd_cuda's matchcost_backward (emd.py:17-21): d cost / d xyz with the match matrix held fixed, nothing through approxmatch; a
+    coincident pair contributes zero.  First order only: the backward is once_differentiable, a double backward raises.  The forward
+    keeps 40 (n + m) bytes per frame, never the (n, m) match matrix."""
+    if torch.is_tensor(xyz1) and xyz1.dim() == 2:
+        xyz1 = xyz1.unsqueeze(0)
+    if torch.is_tensor(xyz2) and xyz2.dim() == 2:
+        xyz2 = xyz2.unsqueeze(0)
+    _chk_cloud("earth_mover_distance", "xyz1", xyz1, channels_first=transpose)
+    _chk_cloud("earth_mover_distance", "xyz2", xyz2, channels_first=transpose)
+    if xyz1.shape[0] != xyz2.shape[0]:
+        raise ValueError("earth_mover_distance: xyz1 and xyz2 disagree on F: xyz1 is %s, xyz2 is %s" % (tuple(xyz1.shape), tuple(xyz2.shape)))
+    _chk_gpu("earth_mover_distance", "xyz1", xyz1)
+    _chk_gpu("earth_mover_distance", "xyz2", xyz2)
+    if transpose:
+        xyz1, xyz2 = xyz1.transpose(1, 2), xyz2.transpose(1, 2)
+    return _EMD.apply(xyz1, xyz2)
+
+
+def emd_loss(pred, gt, reduction="mean"):
+    """The approximate EMD of utils.evaluations.eval_reconstr_frames (evaluations.py:45-46) as a loss: per frame cost / pred.size(-2).
+    pred (F,N,3) or (B,T,N,3), gt the same with its own point count.
+    reduction: "mean" over the frames (a scalar), "sum", or "none" (the per-frame values, (F,) or (B,T))."""
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError("emd_loss: reduction must be 'mean', 'sum' or 'none', got %r" % (reduction,))
+    if not (torch.is_tensor(pred) and torch.is_tensor(gt)) or pred.dim() not in (3, 4) or gt.dim() != pred.dim() or pred.shape[:-2] != gt.shape[:-2]:
+        raise ValueError("emd_loss: pred and gt must both be (F,N,3) or (B,T,N,3) with the same leading sizes, got pred %s, gt %s"
+                         % (tuple(pred.shape) if torch.is_tensor(pred) else type(pred).__name__, tuple(gt.shape) if torch.is_tensor(gt) else type(gt).__name__))
+    lead = pred.shape[:-2]
+    for name, t in (("pred", pred), ("gt", gt)):            # before the reshape, which would silently copy a strided tensor
+        if not t.is_contiguous():
+            raise ValueError("emd_loss: %s must be contiguous (call .contiguous())" % name)
+    p3, g3 = pred.reshape(-1, pred.shape[-2], pred.shape[-1]), gt.reshape(-1, gt.shape[-2], gt.shape[-1])
+    _chk_cloud("emd_loss", "pred", p3)
+    _chk_cloud("emd_loss", "gt", g3)
+    _chk_gpu("emd_loss", "pred", p3)
+    _chk_gpu("emd_loss", "gt", g3)
+    per_frame = _EMD.apply(p3, g3) / p3.shape[1]
     if reduction == "mean":
         return per_frame.mean()
     if reduction == "sum":

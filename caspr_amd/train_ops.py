@@ -403,3 +403,22 @@ def chamfer_bwd(p, q, idx1, idx2, g1=None, g2=None, want_p=True, want_q=True):
     _lib.check(_lib.load().caspr_chamfer_bwd_f32(_p(p), _p(q), B, n, m, _p(idx1), _p(idx2), _p(g1), _p(g2), _p(dp), _p(dq), _stream()),
                "caspr_chamfer_bwd_f32")
     return dp, dq
+
+
+def emd_bwd(p, q, tape, g, want_p=True, want_q=True):
+    """Gradient of ops.earth_mover_distance(p, q, transpose=False, return_tape=True)'s cost with the match held fixed (caspr_emd_bwd_f32;
+    utils/emd.py:17-21): p (B,n,3), q (B,m,3), tape (B,10,n+m) as returned there, g (B,) = dL/d cost.
+    -> (dp (B,n,3) | None, dq (B,m,3) | None): a gradient that is not wanted is not computed.  Fixed summation order, no atomics."""
+    _chk_f32(p, q, tape, g)
+    B, n, _ = p.shape
+    m = q.shape[1]
+    if q.shape[0] != B or p.shape[2] != 3 or q.dim() != 3 or q.shape[2] != 3 or tuple(tape.shape) != (B, 10, n + m):
+        raise ValueError("emd_bwd: p %s, q %s, tape %s disagree (tape must be (B,10,n+m))" % (tuple(p.shape), tuple(q.shape), tuple(tape.shape)))
+    if tuple(g.shape) != (B,):
+        raise ValueError("emd_bwd: g must be (%d,), got %s" % (B, tuple(g.shape)))
+    if not (want_p or want_q):
+        return None, None
+    dp = torch.empty_like(p) if want_p else None
+    dq = torch.empty_like(q) if want_q else None
+    _lib.check(_lib.load().caspr_emd_bwd_f32(_p(p), _p(q), B, n, m, _p(tape), _p(g), _p(dp), _p(dq), _stream()), "caspr_emd_bwd_f32")
+    return dp, dq

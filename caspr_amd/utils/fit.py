@@ -1,20 +1,28 @@
 """Auto-decoding: fit latent codes to observed point clouds through the differentiable decode (models/caspr.py: decode(differentiable=True))
-and the Chamfer loss (losses.py).  The reference has no such routine; its decode is differentiable (caspr.py:204-267 through torchdiffeq)
-and its metric is the Chamfer term of evaluations.py:36-44 -- this is the loop a user would write from the two."""
+and the Chamfer loss or the approximate EMD (losses.py).  The reference has no such routine; its decode is differentiable
+(caspr.py:204-267 through torchdiffeq) and its metrics are the Chamfer term of evaluations.py:36-44 and the EMD of evaluations.py:45-46,
+both differentiable there -- this is the loop a user would write from them."""
 import torch
 
-from ..losses import chamfer_loss
+from ..losses import chamfer_loss, emd_loss
+
+LOSSES = {"chamfer": chamfer_loss, "emd": emd_loss}
 
 
-def fit_latent(model, target, z_init, num_points, steps=100, lr=1e-3, y=None, constant_in_time=False):
+def fit_latent(model, target, z_init, num_points, steps=100, lr=1e-3, y=None, constant_in_time=False, loss="chamfer"):
     """Adam on a copy of z_init (B,T,H) with the model's parameters frozen, minimising
-    chamfer_loss(model.decode(z, y=y, differentiable=True)[2], target), target (B,T,M,3) float32 on the GPU.
+    loss(model.decode(z, y=y, differentiable=True)[2], target), target (B,T,M,3) float32 on the GPU.
+    loss: "chamfer" (losses.chamfer_loss, the default), "emd" (losses.emd_loss: a one-to-one transport cost, which does not let the
+    samples gather on the target's dense regions as a nearest-neighbour loss does), or a callable (x (B,T,num_points,3), target) -> scalar.
     The base samples are drawn ONCE -- decode's own draw for (num_points, constant_in_time), or the given y (B,T,num_points,3) -- and
     reused at every step, so the loss is a deterministic function of z.  Only dL/dz is asked of autograd: no parameter's .grad or
     requires_grad is touched, and the module's state changes only as decode() itself changes it (the device sampler's draw counter, the
     evaluation counters).  -> (z (B,T,H) detached, [loss of every step, before that step's update])."""
     if z_init.dim() != 3:
         raise ValueError("fit_latent: z_init must be (B,T,H), got %s" % (tuple(z_init.shape),))
+    if not callable(loss) and loss not in LOSSES:
+        raise ValueError("fit_latent: loss must be one of %s or a callable (x, target) -> scalar, got %r" % (sorted(LOSSES), loss))
+    loss_fn = loss if callable(loss) else LOSSES[loss]
     B, T, _ = z_init.shape
     z = z_init.detach().clone().requires_grad_(True)
     with torch.no_grad():
@@ -26,8 +34,8 @@ def fit_latent(model, target, z_init, num_points, steps=100, lr=1e-3, y=None, co
     with torch.enable_grad():
         for _ in range(int(steps)):
             x = model.decode(z, num_points, y=y, differentiable=True)[2]
-            loss = chamfer_loss(x, target)
-            z.grad, = torch.autograd.grad(loss, [z])
+            value = loss_fn(x, target)
+            z.grad, = torch.autograd.grad(value, [z])
             opt.step()
-            losses.append(loss.detach())
+            losses.append(value.detach())
     return z.detach(), (torch.stack(losses).cpu().tolist() if losses else [])     # one copy at the end, no sync per step

@@ -504,6 +504,15 @@ long caspr_emd_ws_bytes(int B, int n, int m);
 int caspr_emd_f32(const float *xyz1, const float *xyz2, int B, int n, int m, float *cost, void *ws,
                   long ws_bytes, void *stream);
 
+/* The same cost (bit for bit: the same kernel body, arithmetic and order) for a cost that is differentiated, as the autograd
+ * function of utils/emd.py:5-21 is: it also leaves the TAPE its gradient needs.  The reference saves the (n, m) match matrix
+ * (emd.py:13); here tape (B, 10, n + m) holds, for level i = 0..9 (j = 7..-2), ratioL_i (n floats) then ratioR_i (m floats), which
+ * determine it: match[k,l] = sum_i expf(level_i |p_k - q_l|^2) ratioL_i[k] ratioR_i[l].  tape >= caspr_emd_tape_bytes(B,n,m) =
+ * 40 B (n + m) bytes, ws >= caspr_emd_ws_bytes(B,n,m).  Gradient: caspr_emd_bwd_f32 (caspr_hip_train.h).                       */
+long caspr_emd_tape_bytes(int B, int n, int m);
+int caspr_emd_tape_f32(const float *xyz1, const float *xyz2, int B, int n, int m, float *cost, float *tape, void *ws,
+                       long ws_bytes, void *stream);
+
 /* ---------------- correspondence RANSAC for a rigid pose (utils/evaluations.py:297-437, the camera-pose evaluation;
  * call site evaluations.py:370-375: Open3D registration_ransac_based_on_correspondence, ransac_n = 4, threshold 0.015,
  * RANSACConvergenceCriteria(50000, 5000), point-to-point without scaling) -- src, dst (F,N,row_stride) f32 with

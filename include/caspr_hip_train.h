@@ -105,6 +105,17 @@ int caspr_segment_sum_f32(const float *src, int lds, int col0, const int32_t *se
 int caspr_chamfer_bwd_f32(const float *p, const float *q, int B, int n, int m, const int32_t *idx1, const int32_t *idx2,
                           const float *g1, const float *g2, float *dp, float *dq, void *stream);
 
+/* Approximate-EMD backward (utils/emd.py:17-21: emd_cuda.matchcost_backward on the match matrix the forward saved; the match is held
+ * fixed, nothing flows through approxmatch): xyz1 (B,n,3), xyz2 (B,m,3), tape (B,10,n+m) from caspr_emd_tape_f32, g (B) = dL/d cost.
+ *   match[k,l] = sum_i expf(level_i |p_k - q_l|^2) ratioL_i[k] ratioR_i[l]                  level_i = -4^(7-i), 0 for i = 9
+ *   d1[b,k] =  g[b] sum_l match[k,l] (p_k - q_l) / sqrtf(fmaxf(|p_k - q_l|^2, 1e-20f))      d2[b,l] = -g[b] sum_k (the same term)
+ * Every match entry is rebuilt from the tape in the forward's association, (expf(level d2) * ratioL) * ratioR, so each increment is
+ * the float the forward priced; no (n, m) matrix exists.  d1 (B,n,3) / d2 (B,m,3) are WRITTEN; either may be NULL = not wanted (not
+ * both).  A coincident pair contributes exactly 0.  No float atomics: a thread owns one output point and sums over the other cloud in
+ * index order -> bit-reproducible.  One launch; B <= 65535.                                                                        */
+int caspr_emd_bwd_f32(const float *xyz1, const float *xyz2, int B, int n, int m, const float *tape, const float *g,
+                      float *d1, float *d2, void *stream);
+
 /* GroupNorm(16) over one neighbourhood (ns rows) at a time (PointNetFeatureExtractor, pointnet2.py:
  * 649-703).  Y (NB*ns, ldy).  Forward writes mean/rstd (NB,16) and either the dense activation
  * A = relu?(gn(Y)) or, for the last layer, maxout (NB, ldm) = max over the ns rows and arg (NB,C) =
