@@ -10,11 +10,12 @@ SOURCES = ["point_ops.hip", "gemm.hip", "gemm_bf16x6.hip", "gemm_bf16x6w.hip", "
 EXTRA = {"point_ops.hip": ["-ffp-contract=off"], "emd.hip": ["-ffp-contract=off"], "pose.hip": ["-ffp-contract=off"],
          "cnf_frame_steps.hip": ["-ffp-contract=off"],   # its f64 decisions are restated operation by operation (tests/frame_steps_ref.py)
          "base_sample.hip": ["-ffp-contract=off"],   # its log-density must round as ATen's separate kernels do (see the file's header)
-         # the 64-piece product loop of the bf16x6 CNF kernel must unroll completely (static register indices)
+         # the 64-piece product loop of the 64-point bf16x6 CNF evaluation (ode_x6_eval.inc, included by these four) must unroll
+         # completely (static register indices)
          "ode_bf16x6.hip": ["-mllvm", "-pragma-unroll-threshold=400000"],
-         "ode_dp5.hip": ["-mllvm", "-pragma-unroll-threshold=400000"],   # the same evaluation body
-         "ode_train_fwd.hip": ["-mllvm", "-pragma-unroll-threshold=400000"],   # ... and again (training forward of a CNF block)
-         "ode_sample_tape.hip": ["-mllvm", "-pragma-unroll-threshold=400000"],   # ... and the sampling solve that writes a tape
+         "ode_dp5.hip": ["-mllvm", "-pragma-unroll-threshold=400000"],
+         "ode_train_fwd.hip": ["-mllvm", "-pragma-unroll-threshold=400000"],
+         "ode_sample_tape.hip": ["-mllvm", "-pragma-unroll-threshold=400000"],
          # the 128-point CNF kernel keeps its layer-1 accumulators in the accumulator file BY HAND (inline asm): hipcc's own MFMAs
          # must take the VGPR form there, or it would park them in AGPRs it believes free (see the kernel's header)
          "ode_bf16x6w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
@@ -51,7 +52,7 @@ def _stale(target, deps):
 def build(force=False, verbose=False):
     inc = os.path.join(HERE, "..", "..", "include")
     # (this file is a dependency of every object: the flag set lives here)
-    hdrs = [os.path.abspath(__file__)] + [os.path.join(HERE, h) for h in ("common.h", "ode_x6.h", "ode_x6w_agprs.h", "x6w_common.h", "f16x3_common.h")] + sorted(os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h"))
+    hdrs = [os.path.abspath(__file__)] + [os.path.join(HERE, h) for h in ("common.h", "ode_x6.h", "ode_x6_setup.inc", "ode_x6_eval.inc", "ode_x6w_agprs.h", "x6w_common.h", "f16x3_common.h")] + sorted(os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h"))
     objs, jobs, by_src = [], [], {}
     for s in SOURCES:
         src = os.path.join(HERE, s)

@@ -1,5 +1,5 @@
-// ode_x6.h -- shared between the two bf16x6 point-CNF kernels (ode_bf16x6.hip: 64 points per workgroup, 16x16x32 MFMA,
-// sampling + divergence variants; ode_bf16x6w.hip: 128 points per workgroup, 32x32x16 MFMA, sampling).
+// ode_x6.h -- shared between the bf16x6 point-CNF kernels (ode_bf16x6.hip and the three files that include its evaluation: 64 points
+// per workgroup, 16x16x32 MFMA, sampling + divergence variants; ode_bf16x6w.hip: 128 points per workgroup, 32x32x16 MFMA, sampling).
 #pragma once
 #include "common.h"
 
@@ -60,6 +60,41 @@ struct CnfX6Args {
     unsigned long long *trace;   // debug build: s_memtime stamps of workgroup (0,0), thread 0, RK4 step 0 / stage 1
     int diag;                    // debug build: timing experiments (CASPR_X6_DIAG)
 };
+
+// ---- the 64-point kernels (ode_bf16x6.hip, ode_dp5.hip, ode_train_fwd.hip, ode_sample_tape.hip): LDS layout, the value <-> tangent
+// column exchange and the scheduling regions of the evaluation they share as text (ode_x6_setup.inc, ode_x6_eval.inc)
+#define XC_COLS 64
+#define XC_PA (256 * 64)          // one plane of a piece
+#define XC_PIECE (3 * XC_PA)      // 48 KB: 256 rows x 32 k x 3 planes
+#define XC_NPIECE 32              // per layer: 16 k chunks x 2 row halves
+#define XC_RING 2                 // LDS double buffer of pieces
+#define XC_LDS (XC_RING * XC_PIECE + (6 * XC_H + 3 * XC_H + 3 * XC_H + 8) * 4)
+
+// value of lane (l ^ 8) inside its 16-lane row: the partner column (value <-> tangent) of the same hidden-unit rows
+__device__ __forceinline__ float xc_partner(float v) { return dpp_mov<0x128>(v); }   // row_ror:8
+// tangent lanes (j >= 8 = DPP banks 2, 3 of every row) take the partner's value, value lanes keep their own: ONE
+// v_mov_b32_dpp row_ror:8 bank_mask:0xC in place -- no select, no second register
+__device__ __forceinline__ float xc_value_pre(float v)
+{
+    const int b = __builtin_bit_cast(int, v);
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(b, b, 0x128, 0xf, 0xC, false));
+}
+
+// The scheduling regions of a layer pass (ode_x6_eval.inc explains them where it uses them): sched_group_barrier builds the
+// patterns, sched_barrier(0) closes a region.  Masks: 0x100 = LDS read, 0x008 = MFMA, 0x002 = VALU.
+#define XC_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0);
+#define XC_RM6 XC_SGB(0x100, 2) XC_SGB(0x008, 1) XC_SGB(0x100, 2) XC_SGB(0x008, 1) XC_SGB(0x100, 2) XC_SGB(0x008, 1) XC_SGB(0x100, 2) \
+    XC_SGB(0x008, 1) XC_SGB(0x100, 2) XC_SGB(0x008, 1) XC_SGB(0x100, 2) XC_SGB(0x008, 1)
+#define XC_VM4 XC_SGB(0x002, 2) XC_SGB(0x008, 1) XC_SGB(0x002, 2) XC_SGB(0x008, 1) XC_SGB(0x002, 2) XC_SGB(0x008, 1) XC_SGB(0x002, 2) XC_SGB(0x008, 1)
+#define XC_REGION_PLAIN XC_RM6 XC_SGB(0x008, 18) __builtin_amdgcn_sched_barrier(0);
+#define XC_REGION_TAB XC_RM6 XC_SGB(0x100, 5) XC_SGB(0x008, 18) __builtin_amdgcn_sched_barrier(0);
+#define XC_REGION_VALU_S XC_RM6 XC_VM4 XC_VM4 XC_VM4 XC_VM4 XC_SGB(0x002, 2) XC_SGB(0x008, 2) __builtin_amdgcn_sched_barrier(0);
+// DIV carries ~1.7x the producer VALU (value + tangent forms of the gated softplus): the reads are pinned as in the sampling
+// variant, the VALU is left to the scheduler between the remaining MFMAs (a fixed 2-per-MFMA pattern strands the rest
+// behind the region's last MFMA and sends ~450 registers to scratch)
+#define XC_VM3 XC_SGB(0x002, 3) XC_SGB(0x008, 1) XC_SGB(0x002, 3) XC_SGB(0x008, 1) XC_SGB(0x002, 3) XC_SGB(0x008, 1) XC_SGB(0x002, 3) XC_SGB(0x008, 1)
+#define XC_REGION_VALU_D XC_RM6 XC_VM3 XC_VM3 XC_VM3 XC_VM3 XC_SGB(0x002, 8) XC_SGB(0x008, 2) __builtin_amdgcn_sched_barrier(0);
+#define XC_REGION_VALU if constexpr (DIV) { XC_REGION_VALU_D } else { XC_REGION_VALU_S }   // DIV: a compile-time bool of the including kernel
 
 // ---- the 128-point kernel (ode_bf16x6w.hip)
 #define XW_PTS 128
