@@ -101,6 +101,12 @@ int caspr_group_points_f32(const float *xyz, const float *new_xyz, const float *
  * that have none).  The two calls together write exactly what the plain call writes, bit for bit, in any order.                        */
 #define CASPR_SA_ONLY_MFMA 16
 #define CASPR_SA_ONLY_F64 32
+/* Alignment.  The register kernel (all three widths <= 64) and the f64 re-evaluation of small balls behind it need a 16-byte aligned
+ * output slice: out 16-byte aligned, ldo % 4 == 0, out_off % 4 == 0.  A call on those widths with another slice is NOT refused: it runs
+ * on the LDS kernel, which has no f64 re-evaluation (and no low parts: with CASPR_FEAT_LO_IN / _OUT such a call is refused).  On dense
+ * neighbourhoods that is the same result to f32 rounding; on balls of 2 .. 4 distinct samples it carries the f32 graph's own error,
+ * which is not bounded by 1e-5 -- measured 1.9e-5 against f64 on the (16,16,32) shape at ns = 32 where the aligned call is at 5e-7
+ * (tests/test_sa_mlp_edges.py: test_unaligned_output_slice_falls_back_to_the_lds_kernel records both).  Keep the slice aligned.     */
 int caspr_sa_mlp_max_f32(const float *xyz, const float *new_xyz, const float *feat, int ldf,
                          const int32_t *idx, int B, int n, int M, int C, int ns, int feat_kind,
                          const float *w1p, const float *b1, const float *g1, const float *be1, int C1,
