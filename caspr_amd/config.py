@@ -20,6 +20,8 @@ class KernelConfig:
                                         # its sampling direction (no divergence, n >= 128) on csrc/ode_dp5_f16x3w.hip; opt-in, the default keeps csrc/ode_dp5.hip
     conv_split: str = "f16x3"           # "bf16x6" | "f16x3": the operand split of the persistent 512-channel conv in inference (ops.CONV_SPLIT; csrc/gemm_f16x3w.hip:
                                         # three f16 products per f32 product; the < 512-channel remainder, every other conv and training stay bf16x6)
+    emd_route: str = "frame"            # "frame" | "rows": the forward of the approximate EMD (ops.EMD_ROUTE; csrc/emd.hip).  "frame": one workgroup per frame;
+                                        # "rows": every frame's rows over the grid, 22 launches -- the same ratios and gradient bits, the cost summed in another order; opt-in
     conv_x6w: bool = True               # layers with >= 512 output channels on the persistent 512-channel conv (gemm_bf16x6w.hip)
     x6w_min_cin: int = 512              # ... from this many input channels
     latent_team: bool = True            # the 32-workgroup latent-ODE kernel (False: the single-workgroup kernel)
@@ -46,6 +48,7 @@ _ENV = {
     "CASPR_CNF_SPLIT": ("cnf_split", lambda v: v.strip().lower()),
     "CASPR_CNF_DP5_SPLIT": ("cnf_dp5_split", lambda v: v.strip().lower()),
     "CASPR_CONV_SPLIT": ("conv_split", lambda v: v.strip().lower()),
+    "CASPR_EMD_ROUTE": ("emd_route", lambda v: v.strip().lower()),
     "CASPR_CONV_X6W": ("conv_x6w", lambda v: v != "0"),
     "CASPR_X6W_MIN_CIN": ("x6w_min_cin", int),
     "CASPR_LATENT_TEAM": ("latent_team", lambda v: v != "0"),
@@ -89,6 +92,8 @@ def load(environ=None):
         raise ValueError("CASPR_CNF_DP5_SPLIT must be 'bf16x6' or 'f16x3', got %r" % cfg.cnf_dp5_split)
     if cfg.conv_split not in ("bf16x6", "f16x3"):
         raise ValueError("CASPR_CONV_SPLIT must be 'bf16x6' or 'f16x3', got %r" % cfg.conv_split)
+    if cfg.emd_route not in ("frame", "rows"):
+        raise ValueError("CASPR_EMD_ROUTE must be 'frame' or 'rows', got %r" % cfg.emd_route)
     return cfg
 
 
@@ -100,7 +105,7 @@ def active():
     from . import ops
     from .models import caspr as _c, pointnet2 as _p, tpointnet2 as _t
     d = asdict(config)
-    d.update({"matmul": ops.matmul_mode(), "cnf_split": ops.CNF_SPLIT, "cnf_dp5_split": ops.CNF_DP5_SPLIT, "conv_split": ops.CONV_SPLIT, "conv_x6w": ops.CONV_X6W, "x6w_min_cin": ops._X6W_MIN_CIN, "latent_team": ops.LATENT_TEAM,
+    d.update({"matmul": ops.matmul_mode(), "cnf_split": ops.CNF_SPLIT, "cnf_dp5_split": ops.CNF_DP5_SPLIT, "conv_split": ops.CONV_SPLIT, "emd_route": ops.EMD_ROUTE, "conv_x6w": ops.CONV_X6W, "x6w_min_cin": ops._X6W_MIN_CIN, "latent_team": ops.LATENT_TEAM,
               "early_latent": _c.EARLY_LATENT, "early_latent_team": _c.EARLY_LATENT_TEAM, "sa_lo_parts": _p.LO_PARTS,
               "sa_scale_streams": _p.SCALE_STREAMS, "sa_f64_streams": _p.F64_STREAMS, "fp_commute": _p.FP_COMMUTE, "sa_pre_aggregate": _p.PRE_AGGREGATE, "global_stream": _t.GLOBAL_STREAM, "debug_env": os.environ.get("CASPR_DEBUG", "0") == "1"})
     return d

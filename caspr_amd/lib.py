@@ -121,6 +121,8 @@ SIGNATURES = {
     "caspr_emd_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp, ctypes.c_void_p, c_long, c_stream]),
     "caspr_emd_tape_bytes": (c_long, [c_int, c_int, c_int]),
     "caspr_emd_tape_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, ctypes.c_void_p, c_long, c_stream]),
+    "caspr_emd_rows_ws_bytes": (c_long, [c_int, c_int, c_int]),
+    "caspr_emd_rows_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, ctypes.c_void_p, c_long, c_stream]),
     "caspr_pose_ransac_ws_bytes": (c_long, [c_int, c_int, c_int]),
     "caspr_pose_ransac_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_ulonglong, c_int,
                                       ctypes.c_void_p, c_ip, ctypes.c_void_p, c_ip, ctypes.c_void_p, c_long, c_stream]),

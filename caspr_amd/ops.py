@@ -1505,12 +1505,23 @@ def chamfer_distance(p, q, return_indices=False):
     return d1, d2
 
 
-def earth_mover_distance(xyz1, xyz2, transpose=True, return_tape=False):
+EMD_ROUTE = _cfg.emd_route           # "frame": one workgroup per frame (caspr_emd_f32 / caspr_emd_tape_f32); "rows": the rows of every frame over the grid
+                                     # (caspr_emd_rows_f32: the same ratios bit for bit, the cost summed in another order); opt-in, csrc/emd.hip
+EMD_ROUTES = ("frame", "rows")
+
+
+def earth_mover_distance(xyz1, xyz2, transpose=True, return_tape=False, route=None):
     """`utils.emd.earth_mover_distance` (emd.py:24-45): approximate EMD cost per cloud pair, (b,3,n) inputs when
     `transpose` (as the reference), else (b,n,3).  -> (b,) ; evaluations.py:46 divides by the point count.
     return_tape: -> (cost, tape (b,10,n+m)) from caspr_emd_tape_f32: the same cost bit for bit and the ten levels' ratioL (n) | ratioR (m),
     from which train_ops.emd_bwd rebuilds the match matrix.  No gradient is recorded here: caspr_amd.losses.earth_mover_distance is the
-    differentiable form."""
+    differentiable form.
+    route: None (ops.EMD_ROUTE), "frame" (one workgroup per frame: caspr_emd_f32 / caspr_emd_tape_f32) or "rows" (caspr_emd_rows_f32, with
+    or without the tape: every frame's rows over the grid -- the same tape bit for bit, the cost within rounding of the other route's)."""
+    if route is None:
+        route = EMD_ROUTE
+    if route not in EMD_ROUTES:
+        raise ValueError("earth_mover_distance: route must be 'frame' or 'rows' (None: ops.EMD_ROUTE), got %r" % (route,))
     if xyz1.dim() == 2:
         xyz1 = xyz1.unsqueeze(0)
     if xyz2.dim() == 2:
@@ -1523,14 +1534,21 @@ def earth_mover_distance(xyz1, xyz2, transpose=True, return_tape=False):
     m = xyz2.shape[1]
     cost = torch.empty(B, device=xyz1.device, dtype=torch.float32)
     L = _lib.load()
-    ws = _workspace(L.caspr_emd_ws_bytes(B, n, m), xyz1.device)
+    rows = route == "rows"
+    ws = _workspace(L.caspr_emd_rows_ws_bytes(B, n, m) if rows else L.caspr_emd_ws_bytes(B, n, m), xyz1.device)
     if return_tape:
         if xyz1.dim() != 3 or xyz2.dim() != 3 or xyz1.shape[2] != 3 or xyz2.shape[2] != 3 or xyz2.shape[0] != B:
             raise ValueError("earth_mover_distance: xyz1 (b,n,3) and xyz2 (b,m,3) must agree on b, got %s and %s" % (tuple(xyz1.shape), tuple(xyz2.shape)))
         tape = torch.empty(B, 10, n + m, device=xyz1.device, dtype=torch.float32)
         assert tape.numel() * 4 == L.caspr_emd_tape_bytes(B, n, m)
-        _lib.check(L.caspr_emd_tape_f32(_p(xyz1), _p(xyz2), B, n, m, _p(cost), _p(tape), _p(ws), ws.numel(), _stream()), "caspr_emd_tape_f32")
+        if rows:
+            _lib.check(L.caspr_emd_rows_f32(_p(xyz1), _p(xyz2), B, n, m, _p(cost), _p(tape), _p(ws), ws.numel(), _stream()), "caspr_emd_rows_f32")
+        else:
+            _lib.check(L.caspr_emd_tape_f32(_p(xyz1), _p(xyz2), B, n, m, _p(cost), _p(tape), _p(ws), ws.numel(), _stream()), "caspr_emd_tape_f32")
         return cost, tape
+    if rows:
+        _lib.check(L.caspr_emd_rows_f32(_p(xyz1), _p(xyz2), B, n, m, _p(cost), None, _p(ws), ws.numel(), _stream()), "caspr_emd_rows_f32")
+        return cost
     _lib.check(L.caspr_emd_f32(_p(xyz1), _p(xyz2), B, n, m, _p(cost), _p(ws), ws.numel(), _stream()), "caspr_emd_f32")
     return cost
 

@@ -519,6 +519,17 @@ long caspr_emd_tape_bytes(int B, int n, int m);
 int caspr_emd_tape_f32(const float *xyz1, const float *xyz2, int B, int n, int m, float *cost, float *tape, void *ws,
                        long ws_bytes, void *stream);
 
+/* The same approximate EMD (utils/emd.py:11-12: approxmatch_forward + matchcost_forward; call site utils/evaluations.py:45-46) with the
+ * ROWS of every frame spread over the grid, for batches that do not fill the chip with one workgroup per frame: 22 ordinary launches
+ * on `stream`, grid (row blocks, B), no workgroup waiting for another (csrc/emd.hip).  The ratio vectors are caspr_emd_tape_f32's bit
+ * for bit, so the gradient is too; the cost differs from caspr_emd_f32's only in the order in which the priced increments are added
+ * (one f32 accumulator per row of cloud 1 through the ten levels, then a fixed order that depends on n alone).  A frame's result does
+ * not depend on B, on its place in the batch or on the device.  tape may be NULL (the ratios then live in the workspace); if given it
+ * has caspr_emd_tape_f32's layout and size.  ws >= caspr_emd_rows_ws_bytes(B,n,m); B <= 65535 (grid.y).                           */
+long caspr_emd_rows_ws_bytes(int B, int n, int m);
+int caspr_emd_rows_f32(const float *xyz1, const float *xyz2, int B, int n, int m, float *cost, float *tape, void *ws,
+                       long ws_bytes, void *stream);
+
 /* ---------------- correspondence RANSAC for a rigid pose (utils/evaluations.py:297-437, the camera-pose evaluation;
  * call site evaluations.py:370-375: Open3D registration_ransac_based_on_correspondence, ransac_n = 4, threshold 0.015,
  * RANSACConvergenceCriteria(50000, 5000), point-to-point without scaling) -- src, dst (F,N,row_stride) f32 with
