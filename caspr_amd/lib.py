@@ -123,6 +123,8 @@ SIGNATURES = {
     "caspr_emd_tape_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, ctypes.c_void_p, c_long, c_stream]),
     "caspr_emd_rows_ws_bytes": (c_long, [c_int, c_int, c_int]),
     "caspr_emd_rows_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, ctypes.c_void_p, c_long, c_stream]),
+    "caspr_emd_exact_ws_bytes": (c_long, [c_int, c_int]),
+    "caspr_emd_exact_f32": (c_int, [c_fp, c_fp, c_int, c_int, ctypes.c_double, c_long, c_fp, c_ip, ctypes.c_void_p, c_ip, ctypes.c_void_p, c_long, c_stream]),
     "caspr_pose_ransac_ws_bytes": (c_long, [c_int, c_int, c_int]),
     "caspr_pose_ransac_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_ulonglong, c_int,
                                       ctypes.c_void_p, c_ip, ctypes.c_void_p, c_ip, ctypes.c_void_p, c_long, c_stream]),
@@ -148,6 +150,7 @@ SIGNATURES = {
     "caspr_segment_sum_f32": (c_int, [c_fp, c_int, c_int, c_ip, c_ip, c_fp, c_long, c_int, c_fp, c_int, c_int, c_stream]),
     "caspr_chamfer_bwd_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_ip, c_ip, c_fp, c_fp, c_fp, c_fp, c_stream]),
     "caspr_emd_bwd_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_stream]),
+    "caspr_emd_exact_bwd_f32": (c_int, [c_fp, c_fp, c_ip, c_fp, c_int, c_int, c_fp, c_fp, c_stream]),
     "caspr_gn_rows_f32": (c_int, [c_fp, c_int, c_long, c_int, c_int, c_fp, c_fp, c_float, c_int, c_fp, c_int, c_fp, c_fp, c_fp, c_int, c_ip,
                                   c_stream]),
     "caspr_cnf_act_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_long, c_int, c_int, c_long, c_fp, c_int, c_stream]),

@@ -11,6 +11,11 @@ The approximate EMD of evaluations.py:45-46 (utils/emd.py: an autograd function 
 same way: its forward keeps the ten levels' ratio vectors (40 (n + m) bytes per frame), from which the backward rebuilds every entry of the
 match matrix on the fly -- the published matchcost gradient with the match held fixed, nothing through approxmatch -- again without float
 atomics.  Same rules as ops.py: float32 contiguous GPU tensors, no CPU fallback.
+
+The EXACT EMD -- the cost of the optimal one-to-one assignment, which the reference does not have and its approximation stands for -- is
+exact_earth_mover_distance / emd_exact_loss (caspr_emd_exact_f32: an auction in f64, within n * eps of the optimum with a dual certificate;
+caspr_emd_exact_bwd_f32: the gradient with the matching held fixed, which is the true gradient wherever the optimum is unique).  Equal
+point counts, n <= 2048; the forward keeps the assignment, 4 n bytes per frame.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -159,6 +164,93 @@ def emd_loss(pred, gt, reduction="mean"):
     _chk_gpu("emd_loss", "pred", p3)
     _chk_gpu("emd_loss", "gt", g3)
     per_frame = _EMD.apply(p3, g3) / p3.shape[1]
+    if reduction == "mean":
+        return per_frame.mean()
+    if reduction == "sum":
+        return per_frame.sum()
+    return per_frame.reshape(lead)
+
+
+def _chk_eps(fn, eps):
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not (0.0 < float(eps) < float("inf")):
+        raise ValueError("%s: eps must be positive and finite, got %r" % (fn, eps))
+
+
+class _EMDExact(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, q, eps):
+        p, q = p.contiguous(), q.contiguous()   # the (F,N,3) view of a (F,3,N) input is copied here, as _EMD does
+        cost, assign, _, _ = ops.earth_mover_distance_exact(p, q, transpose=False, eps=eps, return_match=True)
+        ctx.save_for_backward(p, q, assign)
+        ctx.set_materialize_grads(False)        # an unused cost arrives as None: nothing is launched for it
+        return cost
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        p, q, assign = ctx.saved_tensors
+        want_p, want_q = ctx.needs_input_grad[:2]
+        if g is None:
+            return None, None, None
+        return train_ops.emd_exact_bwd(p, q, assign, g.contiguous(), want_p=want_p, want_q=want_q) + (None,)
+
+
+def exact_earth_mover_distance(xyz1, xyz2, transpose=True, eps=1e-6):
+    """The exact EMD of ops.earth_mover_distance_exact with earth_mover_distance's signature and layouts: xyz1, xyz2 (F,3,n) when
+    `transpose`, else (F,n,3), the SAME point count n <= 2048 on both sides; a 2-D cloud is one frame.  float32 contiguous GPU tensors ->
+    cost (F,), the bits of ops.earth_mover_distance_exact (within n * eps of the optimal one-to-one assignment cost), differentiable in
+    whichever input requires grad (the other's gradient is not computed).  The gradient holds the matching fixed -- the true gradient
+    wherever the optimum is unique: d cost / d x_i = (x_i - y_assign[i]) / |x_i - y_assign[i]|, the negative of it on the matched point;
+    a coincident pair contributes zero.  A frame that exhausts the default bid budget (ops.earth_mover_distance_exact: a target of
+    nearly identical points at n >= 1024) has cost NaN and NaN gradients.  First order only: the backward is once_differentiable, a
+    double backward raises.  The forward keeps 4 n bytes per frame (the assignment)."""
+    if torch.is_tensor(xyz1) and xyz1.dim() == 2:
+        xyz1 = xyz1.unsqueeze(0)
+    if torch.is_tensor(xyz2) and xyz2.dim() == 2:
+        xyz2 = xyz2.unsqueeze(0)
+    _chk_cloud("exact_earth_mover_distance", "xyz1", xyz1, channels_first=transpose)
+    _chk_cloud("exact_earth_mover_distance", "xyz2", xyz2, channels_first=transpose)
+    if xyz1.shape[0] != xyz2.shape[0]:
+        raise ValueError("exact_earth_mover_distance: xyz1 and xyz2 disagree on F: xyz1 is %s, xyz2 is %s" % (tuple(xyz1.shape), tuple(xyz2.shape)))
+    _chk_counts("exact_earth_mover_distance", "xyz1", "xyz2", xyz1.shape[2 if transpose else 1], xyz2.shape[2 if transpose else 1])
+    _chk_eps("exact_earth_mover_distance", eps)
+    _chk_gpu("exact_earth_mover_distance", "xyz1", xyz1)
+    _chk_gpu("exact_earth_mover_distance", "xyz2", xyz2)
+    if transpose:
+        xyz1, xyz2 = xyz1.transpose(1, 2), xyz2.transpose(1, 2)
+    return _EMDExact.apply(xyz1, xyz2, eps)
+
+
+def _chk_counts(fn, name1, name2, n, m):
+    if n != m:
+        raise ValueError("%s: a one-to-one assignment needs equal point counts, %s has %d points and %s has %d: use the approximate EMD "
+                         "(earth_mover_distance / emd_loss) for clouds of different sizes" % (fn, name1, n, name2, m))
+    if not 1 <= n <= ops.EMD_EXACT_MAX_POINTS:
+        raise ValueError("%s: %s and %s have %d points: the exact EMD takes 1 .. %d" % (fn, name1, name2, n, ops.EMD_EXACT_MAX_POINTS))
+
+
+def emd_exact_loss(pred, gt, reduction="mean", eps=1e-6):
+    """The exact EMD as a loss: per frame (optimal one-to-one assignment cost) / N, the scale of evaluations.py:46.
+    pred (F,N,3) or (B,T,N,3), gt the same with the SAME point count N <= 2048.
+    reduction: "mean" over the frames (a scalar), "sum", or "none" (the per-frame values, (F,) or (B,T)).
+    eps: the auction's final increment; a frame's cost is within N * eps of the optimum (losses.exact_earth_mover_distance)."""
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError("emd_exact_loss: reduction must be 'mean', 'sum' or 'none', got %r" % (reduction,))
+    _chk_eps("emd_exact_loss", eps)
+    if not (torch.is_tensor(pred) and torch.is_tensor(gt)) or pred.dim() not in (3, 4) or gt.dim() != pred.dim() or pred.shape[:-2] != gt.shape[:-2]:
+        raise ValueError("emd_exact_loss: pred and gt must both be (F,N,3) or (B,T,N,3) with the same leading sizes, got pred %s, gt %s"
+                         % (tuple(pred.shape) if torch.is_tensor(pred) else type(pred).__name__, tuple(gt.shape) if torch.is_tensor(gt) else type(gt).__name__))
+    lead = pred.shape[:-2]
+    for name, t in (("pred", pred), ("gt", gt)):            # before the reshape, which would silently copy a strided tensor
+        if not t.is_contiguous():
+            raise ValueError("emd_exact_loss: %s must be contiguous (call .contiguous())" % name)
+    p3, g3 = pred.reshape(-1, pred.shape[-2], pred.shape[-1]), gt.reshape(-1, gt.shape[-2], gt.shape[-1])
+    _chk_cloud("emd_exact_loss", "pred", p3)
+    _chk_cloud("emd_exact_loss", "gt", g3)
+    _chk_counts("emd_exact_loss", "pred", "gt", p3.shape[1], g3.shape[1])
+    _chk_gpu("emd_exact_loss", "pred", p3)
+    _chk_gpu("emd_exact_loss", "gt", g3)
+    per_frame = _EMDExact.apply(p3, g3, eps) / p3.shape[1]
     if reduction == "mean":
         return per_frame.mean()
     if reduction == "sum":

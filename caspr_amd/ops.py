@@ -1553,6 +1553,72 @@ def earth_mover_distance(xyz1, xyz2, transpose=True, return_tape=False, route=No
     return cost
 
 
+EMD_EXACT_MAX_POINTS = 2048          # what the LDS of one workgroup holds (csrc/emd_exact.hip)
+EMD_EXACT_BIDS_PER_POINT = 4096      # max_bids=None: 4096 n bids per frame
+
+
+def earth_mover_distance_exact(xyz1, xyz2, transpose=True, eps=1e-6, max_bids=None, return_match=False):
+    """The EXACT earth mover's distance between clouds of equal size: the cost of the optimal one-to-one assignment, by a forward auction
+    with epsilon scaling in f64 (caspr_emd_exact_f32, csrc/emd_exact.hip; the reference has only the approximation of emd.py:11-12).
+    Layouts of earth_mover_distance: (b,3,n) inputs when `transpose`, else (b,n,3); a 2-D cloud is one frame.  1 <= n <= 2048.
+    -> cost (b,) f32 = sum_i |p_i - q_assign[i]|, within n * eps of the optimum (the caller divides by n for evaluations.py:46's scale);
+    return_match: -> (cost, assign (b,n) int32 -- a permutation, prices (b,n) f64 -- the dual certificate:
+    cost - (sum_i min_j (c[i,j] + prices[j]) - sum_j prices[j]) <= n * eps, info (b,4) int32 = {converged, phases, rounds, bids}).
+    eps: the final bidding increment, finite and > 0, in the units of the coordinates.
+    max_bids: the bid budget of a frame, 1 .. 2^31 - 1; None: 4096 * n.  That covers ordinary clouds (3-8 n rounds of 5-20 bids), clouds
+    of a few distinct points repeated many times (about 1050 n bids at n = 1024) -- every input measured except a target of (nearly)
+    all-identical points at n >= 1024 (about 4650 n bids at n = 1024).  A frame that exhausts the budget comes back with converged = 0,
+    cost = NaN and assign = -1; nothing is raised here and the other frames are unaffected: look at info[:, 0].
+    Bit-reproducible; a frame's result does not depend on the batch it is in.  No gradient is recorded here:
+    caspr_amd.losses.exact_earth_mover_distance is the differentiable form."""
+    if not (torch.is_tensor(xyz1) and torch.is_tensor(xyz2)):
+        raise ValueError("earth_mover_distance_exact: xyz1 and xyz2 must be tensors, got %s and %s" % (type(xyz1).__name__, type(xyz2).__name__))
+    if xyz1.dim() == 2:
+        xyz1 = xyz1.unsqueeze(0)
+    if xyz2.dim() == 2:
+        xyz2 = xyz2.unsqueeze(0)
+    if transpose and xyz1.dim() == 3 and xyz2.dim() == 3:
+        xyz1, xyz2 = xyz1.transpose(1, 2), xyz2.transpose(1, 2)
+    if xyz1.dim() != 3 or xyz2.dim() != 3 or xyz1.shape[2] != 3 or xyz2.shape[2] != 3 or xyz1.shape[0] != xyz2.shape[0] or xyz1.shape[0] < 1:
+        raise ValueError("earth_mover_distance_exact: xyz1 and xyz2 must be %s with the same b >= 1, got %s and %s"
+                         % ("(b,3,n)" if transpose else "(b,n,3)", tuple(xyz1.shape), tuple(xyz2.shape)))
+    B, n, _ = xyz1.shape
+    m = xyz2.shape[1]
+    if n != m:
+        raise ValueError("earth_mover_distance_exact: a one-to-one assignment needs equal point counts, got n = %d and m = %d: "
+                         "use earth_mover_distance (the approximate EMD) for clouds of different sizes" % (n, m))
+    if not 1 <= n <= EMD_EXACT_MAX_POINTS:
+        raise ValueError("earth_mover_distance_exact: n = %d: a frame lives in the LDS of one workgroup, 1 <= n <= %d" % (n, EMD_EXACT_MAX_POINTS))
+    if B > 65535:
+        raise ValueError("earth_mover_distance_exact: b = %d: b <= 65535" % B)
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not (0.0 < float(eps) < float("inf")):
+        raise ValueError("earth_mover_distance_exact: eps must be positive and finite, got %r" % (eps,))
+    if max_bids is None:
+        max_bids = EMD_EXACT_BIDS_PER_POINT * n
+    if isinstance(max_bids, bool) or not isinstance(max_bids, int) or not 1 <= max_bids <= 2 ** 31 - 1:
+        raise ValueError("earth_mover_distance_exact: max_bids must be an integer in 1 .. 2^31 - 1 (None: %d * n), got %r"
+                         % (EMD_EXACT_BIDS_PER_POINT, max_bids))
+    for name, t in (("xyz1", xyz1), ("xyz2", xyz2)):   # the type first, the device last: what is wrong with a tensor is said wherever it lives
+        if t.dtype != torch.float32:
+            raise TypeError("earth_mover_distance_exact: %s must be float32, got %s" % (name, t.dtype))
+    for name, t in (("xyz1", xyz1), ("xyz2", xyz2)):
+        if not t.is_cuda:
+            raise ValueError("earth_mover_distance_exact: %s is on %s: caspr_amd kernels need tensors on the GPU, there is no CPU fallback" % (name, t.device))
+        _on_current_device(t)
+    xyz1, xyz2 = xyz1.contiguous(), xyz2.contiguous()   # the (b,n,3) view of a (b,3,n) input is copied, as earth_mover_distance does
+    dev = xyz1.device
+    cost = torch.empty(B, device=dev, dtype=torch.float32)
+    assign = torch.empty(B, n, device=dev, dtype=torch.int32)
+    prices = torch.empty(B, n, device=dev, dtype=torch.float64)
+    info = torch.empty(B, 4, device=dev, dtype=torch.int32)
+    L = _lib.load()
+    need = L.caspr_emd_exact_ws_bytes(B, n)
+    ws = _workspace(need, dev) if need else None
+    _lib.check(L.caspr_emd_exact_f32(_p(xyz1), _p(xyz2), B, n, float(eps), int(max_bids), _p(cost), _p(assign), _p(prices), _p(info),
+                                     _p(ws), ws.numel() if ws is not None else 0, _stream()), "caspr_emd_exact_f32")
+    return (cost, assign, prices, info) if return_match else cost
+
+
 def ransac_rigid_from_correspondences(src, dst, threshold=0.015, num_hypotheses=5000, sample_size=4, seed=0, refine=False):
     """Open3D `registration_ransac_based_on_correspondence` with point-to-point estimation without scaling, as the camera-pose
     evaluation calls it (evaluations.py:370-375: ransac_n = 4, threshold 0.015, RANSACConvergenceCriteria(50000, 5000) ->

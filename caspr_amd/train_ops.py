@@ -422,3 +422,25 @@ def emd_bwd(p, q, tape, g, want_p=True, want_q=True):
     dq = torch.empty_like(q) if want_q else None
     _lib.check(_lib.load().caspr_emd_bwd_f32(_p(p), _p(q), B, n, m, _p(tape), _p(g), _p(dp), _p(dq), _stream()), "caspr_emd_bwd_f32")
     return dp, dq
+
+
+def emd_exact_bwd(p, q, assign, g, want_p=True, want_q=True):
+    """Gradient of ops.earth_mover_distance_exact(p, q, transpose=False, return_match=True)'s cost with the matching held fixed
+    (caspr_emd_exact_bwd_f32; the place of utils/emd.py:17-21): p, q (B,n,3), assign (B,n) int32 as returned there, g (B,) = dL/d cost.
+    -> (dp (B,n,3) | None, dq (B,n,3) | None): a gradient that is not wanted is not computed.  dp_i = g (p_i - q_assign[i]) / |.|, dq_j the
+    negative of the term of the i matched to j; a coincident pair contributes zero, a frame with assign = -1 gets NaN.  No atomics."""
+    _chk_f32(p, q, g)
+    if p.dim() != 3 or q.dim() != 3 or p.shape[2] != 3 or tuple(q.shape) != tuple(p.shape):
+        raise ValueError("emd_exact_bwd: p %s and q %s must both be (B,n,3)" % (tuple(p.shape), tuple(q.shape)))
+    B, n, _ = p.shape
+    if not torch.is_tensor(assign) or assign.dtype != torch.int32 or tuple(assign.shape) != (B, n) or not assign.is_contiguous() or assign.device != p.device:
+        raise ValueError("emd_exact_bwd: assign must be a contiguous int32 (%d,%d) tensor on %s, got %s %s"
+                         % (B, n, p.device, getattr(assign, "dtype", type(assign).__name__), tuple(getattr(assign, "shape", ()))))
+    if tuple(g.shape) != (B,):
+        raise ValueError("emd_exact_bwd: g must be (%d,), got %s" % (B, tuple(g.shape)))
+    if not (want_p or want_q):
+        return None, None
+    dp = torch.empty_like(p) if want_p else None
+    dq = torch.empty_like(q) if want_q else None
+    _lib.check(_lib.load().caspr_emd_exact_bwd_f32(_p(p), _p(q), _p(assign), _p(g), B, n, _p(dp), _p(dq), _stream()), "caspr_emd_exact_bwd_f32")
+    return dp, dq

@@ -14,6 +14,9 @@ def fit_latent(model, target, z_init, num_points, steps=100, lr=1e-3, y=None, co
     loss(model.decode(z, y=y, differentiable=True)[2], target), target (B,T,M,3) float32 on the GPU.
     loss: "chamfer" (losses.chamfer_loss, the default), "emd" (losses.emd_loss: a one-to-one transport cost, which does not let the
     samples gather on the target's dense regions as a nearest-neighbour loss does), or a callable (x (B,T,num_points,3), target) -> scalar.
+    The EXACT one-to-one transport cost goes in as a callable: fit_latent(..., loss=losses.emd_exact_loss) descends the gradient of the
+    optimal assignment itself (emd_loss's goes through a match matrix that meets its marginals only approximately); it needs
+    num_points == M <= 2048.
     The base samples are drawn ONCE -- decode's own draw for (num_points, constant_in_time), or the given y (B,T,num_points,3) -- and
     reused at every step, so the loss is a deterministic function of z.  Only dL/dz is asked of autograd: no parameter's .grad or
     requires_grad is touched, and the module's state changes only as decode() itself changes it (the device sampler's draw counter, the

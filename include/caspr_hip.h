@@ -530,6 +530,38 @@ long caspr_emd_rows_ws_bytes(int B, int n, int m);
 int caspr_emd_rows_f32(const float *xyz1, const float *xyz2, int B, int n, int m, float *cost, float *tape, void *ws,
                        long ws_bytes, void *stream);
 
+/* ---------------- EXACT EMD: the cost of the optimal one-to-one assignment between two clouds of equal size (csrc/emd_exact.hip).
+ * The reference has only the approximation (utils/emd.py:11-12: approxmatch_forward + matchcost_forward; call site
+ * utils/evaluations.py:45-46); this entry is what that approximation stands for, and the yardstick it is measured against.
+ * xyz1, xyz2 (B,n,3) f32 ->
+ *   cost (B) f32 = sum_i c[i, assign[i]];  assign (B,n) int32, a permutation: the point of cloud 2 matched to point i of cloud 1;
+ *   prices (B,n) f64: the final object prices, the dual certificate;  info (B,4) int32 = {converged 0/1, phases, rounds, bids}.
+ * Semantics (tests/emd_exact_ref.py restates them in numpy; assign and prices agree with it bit for bit):
+ *   cost matrix   c[i,j] = sqrtf(dx*dx + dy*dy + dz*dz) in f32 in exactly that association, promoted to f64; never stored, recomputed
+ *                 from the clouds held in LDS.
+ *   auction       forward Jacobi auction in f64.  In each round every unassigned point i of cloud 1 takes v[j] = -c[i,j] - p[j] over all
+ *                 j, the best value v1 at the LOWEST such j = j1 and the second-best value v2 over j != j1 (n = 1: v2 = v1), and bids
+ *                 (p[j1] + (v1 - v2)) + eps_k on j1.  Every object takes its highest bid, ties to the lowest bidder index: its price
+ *                 becomes the bid, its previous owner becomes unassigned, the winner is assigned.  All bids of a round are computed from
+ *                 the prices at the start of the round.
+ *   eps scaling   eps_0 = max(D/4, eps), D = sqrtf(ex*ex + ey*ey + ez*ez) in f32 with e the extent of the bounding box of both clouds
+ *                 of the frame; eps_{k+1} = max(eps_k / 5, eps); the last phase runs at exactly eps.  Each phase keeps the prices and
+ *                 clears the assignment; prices start at 0.
+ *   guarantee     at convergence sum_i c[i,assign[i]] - (sum_i min_j (c[i,j] + p[j]) - sum_j p[j]) <= n eps, and the subtrahend is a
+ *                 lower bound of the optimum: the cost is within n eps of the earth mover's distance, checkable from prices alone.
+ *   scheduling    the bid maximum is a 64-bit integer max on the bid's bit pattern and the tie-break an integer max on the bidder index:
+ *                 no float atomics, a frame's outputs do not depend on the wave schedule, on B or on its place in the batch.
+ *   bounds        a frame stops when its bid count would pass max_bids (a round posts >= 1 bid, so rounds <= max_bids), after 64 phases,
+ *                 or when no object has a value above -inf (non-finite input).  A stopped frame writes converged = 0, cost = NaN,
+ *                 assign = -1, the prices and counts it reached; the other frames are unaffected.  No spin, no cross-workgroup wait, no
+ *                 host read and no deferred status: the caller looks at info.
+ * One workgroup per frame.  1 <= n <= 2048 (what the LDS of a workgroup holds), 1 <= B <= 65535, eps finite and > 0,
+ * 1 <= max_bids <= 2^31 - 1, ws_bytes >= caspr_emd_exact_ws_bytes(B,n) (0 today: ws may be NULL; the entry stays so that the limit on n
+ * can move); anything else is refused before any launch.  Gradient: caspr_emd_exact_bwd_f32 (caspr_hip_train.h).                    */
+long caspr_emd_exact_ws_bytes(int B, int n);
+int caspr_emd_exact_f32(const float *xyz1, const float *xyz2, int B, int n, double eps, long max_bids, float *cost, int32_t *assign,
+                        double *prices, int32_t *info, void *ws, long ws_bytes, void *stream);
+
 /* ---------------- correspondence RANSAC for a rigid pose (utils/evaluations.py:297-437, the camera-pose evaluation;
  * call site evaluations.py:370-375: Open3D registration_ransac_based_on_correspondence, ransac_n = 4, threshold 0.015,
  * RANSACConvergenceCriteria(50000, 5000), point-to-point without scaling) -- src, dst (F,N,row_stride) f32 with

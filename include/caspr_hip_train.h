@@ -116,6 +116,17 @@ int caspr_chamfer_bwd_f32(const float *p, const float *q, int B, int n, int m, c
 int caspr_emd_bwd_f32(const float *xyz1, const float *xyz2, int B, int n, int m, const float *tape, const float *g,
                       float *d1, float *d2, void *stream);
 
+/* Exact-EMD backward (the place of utils/emd.py:17-21 for caspr_emd_exact_f32; the reference has only the approximation's gradient):
+ * xyz1, xyz2 (B,n,3), assign (B,n) from caspr_emd_exact_f32, gcost (B) = dL/d cost.  With the matching held fixed -- the true gradient
+ * wherever the optimum is unique --
+ *   gxyz1[b,i] = gcost[b] (x_i - y_assign[i]) / |x_i - y_assign[i]|      gxyz2[b,j] = -(the term of the one i with assign[i] = j)
+ * the term formed in f64 from the f32 coordinates and rounded once; the i of an object is found through the inverse permutation, built
+ * in LDS.  gxyz1 / gxyz2 (B,n,3) are WRITTEN; either may be NULL = not wanted (not both).  A coincident pair contributes exactly 0 (the
+ * convention of caspr_emd_bwd_f32).  A frame whose assign holds an index outside 0..n-1 (the -1 of a frame that did not converge) gets
+ * NaN in every component.  No atomics, one thread per output point -> bit-reproducible.  One launch; n <= 2048, B <= 65535.        */
+int caspr_emd_exact_bwd_f32(const float *xyz1, const float *xyz2, const int32_t *assign, const float *gcost, int B, int n,
+                            float *gxyz1, float *gxyz2, void *stream);
+
 /* GroupNorm(16) over one neighbourhood (ns rows) at a time (PointNetFeatureExtractor, pointnet2.py:
  * 649-703).  Y (NB*ns, ldy).  Forward writes mean/rstd (NB,16) and either the dense activation
  * A = relu?(gn(Y)) or, for the last layer, maxout (NB, ldm) = max over the ns rows and arg (NB,C) =
