@@ -825,6 +825,63 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const float *__restrict
     }
 }
 
+// The same partials for groups whose width is NOT a multiple of 4 (560 channels in 16 groups of 35: a layer conv1x1_gn's fused route
+// takes at P % 128 == 0 and hands to this pass at any other row count, or in f32 mode): one thread per (row lane, channel), scalar
+// loads -- a group's channels no longer fall on 16-byte quads.  Same layout of psum / pmm, same f64 sums in a fixed order.
+__global__ __launch_bounds__(256) void gn_partial_scalar_kernel(const float *__restrict__ Y, int ldy, int P, int C, int G,
+                                                                double *__restrict__ psum, float *__restrict__ pmm)
+{
+    __shared__ double s_sum[256], s_sq[256];
+    __shared__ float s_mx[256], s_mn[256];
+    const int g = blockIdx.x, s = blockIdx.y, b = blockIdx.z, S = gridDim.y;
+    const int cpg = C / G;  // host guarantees cpg <= 256
+    const int TP = 256 / cpg;
+    const int tc = threadIdx.x % cpg, tp = threadIdx.x / cpg;
+    const int pbeg = s * GN_SPLIT, pend = (pbeg + GN_SPLIT) < P ? (pbeg + GN_SPLIT) : P;
+    double sum = 0.0, sq = 0.0;
+    float mx = -INFINITY, mn = INFINITY;
+    if (tp < TP) {
+        const float *base = Y + (long)b * P * ldy + g * cpg + tc;
+#pragma unroll 4
+        for (int p = pbeg + tp; p < pend; p += TP) {
+            const float v = base[(long)p * ldy];
+            sum += (double)v;
+            sq += (double)v * (double)v;
+            mx = v > mx ? v : mx;
+            mn = v < mn ? v : mn;
+        }
+    }
+    s_sum[threadIdx.x] = sum;
+    s_sq[threadIdx.x] = sq;
+    s_mx[threadIdx.x] = mx;
+    s_mn[threadIdx.x] = mn;
+    __syncthreads();
+    for (int off = 128; off >= 1; off >>= 1) {
+        if (threadIdx.x < off) {
+            s_sum[threadIdx.x] += s_sum[threadIdx.x + off];
+            s_sq[threadIdx.x] += s_sq[threadIdx.x + off];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        double *o = psum + (((long)b * G + g) * S + s) * 2;
+        o[0] = s_sum[0];
+        o[1] = s_sq[0];
+    }
+    if (threadIdx.x < cpg) {  // one thread per channel of the group folds the TP row partials
+        const int c = threadIdx.x;
+        float m1 = -INFINITY, m0 = INFINITY;
+        for (int r = 0; r < TP; ++r) {
+            const float a = s_mx[r * cpg + c], bb = s_mn[r * cpg + c];
+            m1 = a > m1 ? a : m1;
+            m0 = bb < m0 ? bb : m0;
+        }
+        float *o = pmm + (((long)b * C + g * cpg + c) * S + s) * 2;
+        o[0] = m1;
+        o[1] = m0;
+    }
+}
+
 // The same partials with ROW-contiguous reads, for C <= 1024: one workgroup per (point split, batch entry) covers all channels --
 // thread (tp, tq) walks rows tp, tp + TP, ... of the split with the 16 bytes of channel quad tq, so a wave reads whole rows
 // (gn_partial_kernel above gives every group its own workgroup: at 4 channels per group each reads 16 bytes per row, a quarter
@@ -933,7 +990,7 @@ static int gn_stats_impl(const float *Y, int ldy, int B, int P, int C, int G, co
                          long ws_bytes, void *stream)
 {
     CASPR_REQUIRE(Y && gamma && beta && scale && shift && ws && B > 0 && P > 0 && C > 0 && G > 0, "gn_stats: bad arguments");
-    CASPR_REQUIRE(C % G == 0 && (C / G) % 4 == 0 && (C / G) <= 256, "gn_stats: C/G=%d must be a multiple of 4 and <= 256", C / G);
+    CASPR_REQUIRE(C % G == 0 && (C / G) <= 256, "gn_stats: C=%d must be a multiple of G=%d, C/G <= 256", C, G);
     CASPR_REQUIRE(ldy % 4 == 0 && ldy >= C && ((uintptr_t)Y % 16) == 0, "gn_stats: ldy=%d must be a multiple of 4 and >= C", ldy);
     CASPR_REQUIRE(ws_bytes >= caspr_gn_ws_bytes(B, P, C, G), "gn_stats: workspace too small (%ld < %ld)", ws_bytes, caspr_gn_ws_bytes(B, P, C, G));
     CASPR_REQUIRE(B <= 65535, "gn_stats: B too large");
@@ -941,7 +998,9 @@ static int gn_stats_impl(const float *Y, int ldy, int B, int P, int C, int G, co
     double *psum = (double *)ws;
     float *pmm = (float *)((char *)ws + (((long)B * G * S * 16 + 63) & ~63L));
     hipStream_t st = (hipStream_t)stream;
-    if (C <= 1024 && G <= 256 && 256 % (C >> 2) == 0)
+    if ((C / G) % 4 != 0)
+        gn_partial_scalar_kernel<<<dim3(G, S, B), dim3(256), 0, st>>>(Y, ldy, P, C, G, psum, pmm);
+    else if (C <= 1024 && G <= 256 && 256 % (C >> 2) == 0)
         gn_partial_rows_kernel<<<dim3(S, B), dim3(256), 0, st>>>(Y, ldy, P, C, G, psum, pmm);
     else
         gn_partial_kernel<<<dim3(G, S, B), dim3(256), 0, st>>>(Y, ldy, P, C, G, psum, pmm);

@@ -298,7 +298,8 @@ int caspr_conv_gn_finalize_f32(const void *ws, long ws_bytes, int B, int P, int 
  *   scale[b,c] = gamma[c]*rstd[b,g(c)] ; shift[b,c] = beta[c] - mean[b,g(c)]*scale[b,c]
  * and, when pmax != NULL, pmax[b,c] = max_p (Y[b,p,c]*scale+shift) (tpointnet2.py:111, pointnet.py:42).
  * Two deterministic passes (f64 partial sums per 1024-point split, then a fixed-order combine);
- * ws = caller-provided scratch of at least caspr_gn_ws_bytes(B,P,C,G) bytes.  C/G %% 4 == 0.       */
+ * ws = caller-provided scratch of at least caspr_gn_ws_bytes(B,P,C,G) bytes.  C/G <= 256 (a width that is
+ * no multiple of 4 takes a scalar-load form of the first pass).                                        */
 long caspr_gn_ws_bytes(int B, int P, int C, int G);
 int caspr_gn_stats_f32(const float *Y, int ldy, int B, int P, int C, int G, const float *gamma,
                        const float *beta, float eps, float *scale, float *shift, float *pmax,

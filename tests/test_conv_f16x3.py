@@ -2,7 +2,7 @@
 against the f64 contraction at test_conv1x1_x6w_kernel's tolerance 2e-6 max(1, |y64|max), its GroupNorm statistics against the other
 conv route's at 3e-6 max(1, .), conv1x1_gn / batch / piece / grid invariance bit for bit, the weight scale found on the device, and the
 range guard.  Shapes: the smallest at which the stream of chunks can go wrong (one chunk per tile, odd chunk counts, two channel tiles,
-a remainder on the tail kernel, Cin not a multiple of 64)."""
+a remainder on the tail kernel, one above 64 channels on the 256-channel kernel, Cin not a multiple of 64)."""
 import numpy as np
 import pytest
 import torch
@@ -11,7 +11,7 @@ from test_hip_parity import exact, record, rnd
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(1, 128, 32, 512), (1, 128, 64, 512), (1, 256, 96, 1024), (3, 128, 512, 560), (2, 384, 544, 1536)]
+SHAPES = [(1, 128, 32, 512), (1, 128, 64, 512), (1, 256, 96, 1024), (3, 128, 512, 560), (2, 384, 544, 1536), (2, 128, 64, 704)]
 
 
 @pytest.fixture(autouse=True)
