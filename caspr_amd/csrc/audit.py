@@ -1,4 +1,4 @@
-"""Code-object audit of the kernels that manage the accumulator file by hand (ode_bf16x6w.hip, its f16x3 copy ode_f16x3w.hip, the adaptive solve on that copy ode_dp5_f16x3w.hip, gemm_bf16x6w.hip, its f16x3 copy gemm_f16x3w.hip).
+"""Code-object audit of the kernels that manage the accumulator file by hand (ode_bf16x6w.hip, its f16x3 copy ode_f16x3w.hip, the adaptive solve ode_dp5_f16x3w.hip on the same evaluation text (ode_h3w_eval.inc), gemm_bf16x6w.hip, its f16x3 copy gemm_f16x3w.hip).
 
 Both keep 256 live values at FIXED addresses a0..a255 across separate inline-asm statements.  A clobber list does not reserve
 registers between statements: what keeps hipcc out of the AGPRs is the hidden flag -amdgpu-mfma-vgpr-form (build.py EXTRA) plus the
@@ -136,8 +136,8 @@ def audit_cnf_h3w(obj):
 
 
 def audit_cnf_dp5_h3w(obj):
-    """cnf_dp5_h3w_kernel (ode_dp5_f16x3w.hip: the adaptive Dormand-Prince loop around the evaluation of the kernel above): the contract
-    of audit_cnf_h3w -- no scratch, agpr_count 256, exactly the accumulator moves the source writes (ONE copy of the stage body: 256
+    """cnf_dp5_h3w_kernel (ode_dp5_f16x3w.hip: the adaptive Dormand-Prince loop around the evaluation of the kernel above, one text with it): the contract
+    of audit_cnf_h3w -- no scratch, agpr_count 256, exactly the accumulator moves the source writes (the stage body ONCE in the code: 256
     zeroing writes + 256 plane writes; 256 reads in pass 0, 256 plane reads in passes 1-3) and no v_accvgpr_mov, layer 1's MFMAs (8
     pieces x 4 regions x 6) on a[..], every other MFMA in the VGPR form, all of them v_mfma_f32_32x32x16_f16, M0 touched by the LDS-DMA
     statements only.  Also returned, not judged: cvt_pk, and vgpr_count, the metadata's `.vgpr_count` -- on gfx950 the COMBINED register count of a wave, the

@@ -20,8 +20,8 @@ EXTRA = {"point_ops.hip": ["-ffp-contract=off"], "emd.hip": ["-ffp-contract=off"
          # the 128-point CNF kernel keeps its layer-1 accumulators in the accumulator file BY HAND (inline asm): hipcc's own MFMAs
          # must take the VGPR form there, or it would park them in AGPRs it believes free (see the kernel's header)
          "ode_bf16x6w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
-         "ode_f16x3w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],   # the same, on f16
-         "ode_dp5_f16x3w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],   # ... and its evaluation under the adaptive loop
+         "ode_f16x3w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],   # the same, on f16 (ode_h3w_eval.inc)
+         "ode_dp5_f16x3w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],   # ... the same text under the adaptive loop
          "gemm_bf16x6w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
          "gemm_f16x3w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"]}   # its f16x3 copy
 # CASPR_BUILD_DEBUG=1: the flavour with phase-trace hooks and experiment switches (-DCASPR_DEBUG_HOOKS, see common.h), built
@@ -50,10 +50,15 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force=False, verbose=False):
+def deps():
+    """What every object depends on besides its source: this file (the flag set lives here), every header and every text fragment of
+    this directory, the public headers.  Listed from the directories: a fragment that is missing here leaves a stale object behind."""
     inc = os.path.join(HERE, "..", "..", "include")
-    # (this file is a dependency of every object: the flag set lives here)
-    hdrs = [os.path.abspath(__file__)] + [os.path.join(HERE, h) for h in ("common.h", "ode_x6.h", "ode_x6_setup.inc", "ode_x6_eval.inc", "ode_x6w_agprs.h", "x6w_common.h", "f16x3_common.h")] + sorted(os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h"))
+    return [os.path.abspath(__file__)] + sorted(os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith((".h", ".inc"))) + sorted(os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h"))
+
+
+def build(force=False, verbose=False):
+    hdrs = deps()
     objs, jobs, by_src = [], [], {}
     for s in SOURCES:
         src = os.path.join(HERE, s)

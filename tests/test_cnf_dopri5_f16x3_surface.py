@@ -52,6 +52,23 @@ def test_build_list_and_audit_carry_the_new_file():
     assert os.path.exists(os.path.join(ROOT, "caspr_amd", "csrc", NEW))
 
 
+def test_the_stage_body_is_one_text_and_every_fragment_is_a_build_dependency():
+    import glob
+    from caspr_amd.csrc import build
+    csrc = os.path.join(ROOT, "caspr_amd", "csrc")
+    frag = "ode_h3w_eval.inc"
+    for f in ("ode_f16x3w.hip", NEW):
+        assert '#include "%s"' % frag in open(os.path.join(csrc, f)).read()
+    # the f16x3 CNF sources: the two kernels' files and what is shared between them
+    srcs = ["ode_f16x3w.hip", NEW] + sorted(os.path.basename(p) for p in glob.glob(os.path.join(csrc, "ode_h3w*")))
+    assert frag in srcs
+    for stmt in ("auto region_a = ", "auto l2_step = ", "auto piece_head = "):
+        assert [f for f in srcs if stmt in open(os.path.join(csrc, f)).read()] == [frag], stmt
+    deps = {os.path.abspath(p) for p in build.deps()}
+    shared = {os.path.abspath(p) for p in glob.glob(os.path.join(csrc, "*")) if p.endswith((".h", ".inc"))}
+    assert os.path.abspath(os.path.join(csrc, frag)) in shared and shared <= deps
+
+
 def test_state_dict_key_surface_is_unchanged(monkeypatch):
     from caspr_amd import ops
     from caspr_amd.models import CaSPR
