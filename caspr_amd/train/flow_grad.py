@@ -18,6 +18,8 @@ activation into the GEMM epilogue and recomputing instead of storing the layer p
 The SAMPLING direction of the point CNF (decode(differentiable=True); cnf.py:70-128 with reverse = True, caspr.py:262) is at the end of the
 file: CnfSampleSolve / point_cnf_sample_train, one node per block on value rows only.
 """
+import weakref
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -25,24 +27,47 @@ import torch.nn.functional as F
 from .. import ops
 from .. import train_ops as T
 
-_pack_cache = {}
+_pack_cache = {}     # id(parameter) -> (weakref to THAT parameter, {transposed: (signature, PackedWeight, alias of the storage)})
 
 
 def _packed(w, transposed):
-    """PackedWeight of a 2-D weight; cached for nn.Parameters (keyed on storage + version), fresh for temporaries."""
+    """PackedWeight of a 2-D weight; cached for nn.Parameters (keyed on storage + version), fresh for temporaries.
+    An entry belongs to one parameter OBJECT and dies with it: ids, addresses and version counters all repeat between a dead
+    module and the next one built the same way, so the id only finds the entry, the weak reference (`is`) decides, and its
+    callback evicts.  (No WeakKeyDictionary: it compares keys with ==, which is element-wise on tensors.)  The alias of the
+    storage keeps the address of the signature from being handed out again while the entry lives (utils/weight_cache.py)."""
     def build():
         src = w.detach()
         return ops.PackedWeight((src.t() if transposed else src).contiguous())
     if not isinstance(w, nn.Parameter):
         return build()
-    key = (id(w), transposed)
-    sig = (w.data_ptr(), w._version)
-    hit = _pack_cache.get(key)
+    key = id(w)
+    ent = _pack_cache.get(key)
+    if ent is None or ent[0]() is not w:
+        def evict(ref, key=key, cache=_pack_cache):
+            cur = cache.get(key)
+            if cur is not None and cur[0] is ref:
+                del cache[key]
+        ent = _pack_cache[key] = (weakref.ref(w, evict), {})
+    sig = (w.data_ptr(), w._version, w.device)
+    hit = ent[1].get(transposed)
     if hit is not None and hit[0] == sig:
         return hit[1]
     pw = build()
-    _pack_cache[key] = (sig, pw)
+    ent[1][transposed] = (sig, pw, w.detach())
     return pw
+
+
+def drop_packs(params=None):
+    """Forget the cached packs of `params` (an iterable of parameters; None: of every parameter).  utils.weight_cache.invalidate()
+    calls it after in-place writes through `.data`, which no signature sees."""
+    if params is None:
+        _pack_cache.clear()
+        return
+    for p in params:
+        ent = _pack_cache.get(id(p))
+        if ent is not None and ent[0]() is p:
+            del _pack_cache[id(p)]
 
 
 def _pad4(x):

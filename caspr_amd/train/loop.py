@@ -173,23 +173,26 @@ def broadcast_model(model, src=0):
     """Every replica starts from rank `src`'s parameters AND buffers (MovingBatchNorm running statistics, step counters): the
     reference's nn.DataParallel replicates module 0 on every forward (train.py:131-132); with one process per GPU the replicas
     agree only if they start equal and apply the same averaged gradient -- whatever seed each rank initialised with.  One
-    flat broadcast per dtype.  No-op without an initialised process group."""
+    flat broadcast per dtype.  No-op without an initialised process group.
+    The received values are written through the parameters and buffers THEMSELVES under no_grad, not through `.data`: a write through
+    `.data` leaves `_version` where it was, and the packed weights a replica built before the call (a warm-up, calibrate_rk4_steps, a
+    validation pass) would go on standing for its own seed's parameters (utils/weight_cache.py)."""
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
         return
-    tensors = [p.data for p in model.parameters()] + [b.data for b in model.buffers()]
     seen, uniq = set(), []
-    for t in tensors:                      # latent_ode.solver.ode_func.* aliases latent_ode.ode_func.*
+    for t in list(model.parameters()) + list(model.buffers()):      # latent_ode.solver.ode_func.* aliases latent_ode.ode_func.*
         if t.data_ptr() not in seen and t.numel():
             seen.add(t.data_ptr())
             uniq.append(t)
-    for dt in sorted({t.dtype for t in uniq}, key=str):
-        group = [t for t in uniq if t.dtype == dt]
-        flat = torch.cat([t.reshape(-1) for t in group])
-        dist.broadcast(flat, src)
-        off = 0
-        for t in group:
-            t.copy_(flat[off:off + t.numel()].view_as(t))
-            off += t.numel()
+    with torch.no_grad():
+        for dt in sorted({t.dtype for t in uniq}, key=str):
+            group = [t for t in uniq if t.dtype == dt]
+            flat = torch.cat([t.detach().reshape(-1) for t in group])
+            dist.broadcast(flat, src)
+            off = 0
+            for t in group:
+                t.copy_(flat[off:off + t.numel()].view_as(t))
+                off += t.numel()
 
 
 def train_step(model, optimizer, pcl_in, nocs_out, cnf_loss_weight=0.01, tnocs_loss_weight=100.0, bucket=None, e=None):

@@ -260,7 +260,6 @@ def test_cnf_block_vs_f64_oracle(monkeypatch, seeded_sd, stress_sd, route, BT, n
     monkeypatch.setattr(O, "GRAD_MODE", True)
     monkeypatch.setattr(FG, "HIDDEN_NODE", route != "no_hidden_node")
     monkeypatch.setattr(FG, "OUT_NODE", route != "no_out_node")
-    monkeypatch.setattr(FG, "_pack_cache", {})     # packed weights are cached by parameter identity: none from an earlier block
     sd = seeded_sd if weights == "seeded" else stress_sd
     pre = "point_cnf.chain.1"
     m = CaSPR(cnf_rk4_steps=steps)
