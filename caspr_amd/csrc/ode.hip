@@ -26,6 +26,7 @@
 // advects up to 16 sequences at once: the batch is the N=16 column dimension of the f32 MFMA tile, the
 // hidden state is an LDS B-tile, each wave owns 64 of the 512 hidden units and streams its packed
 // weights from L2 (read once per evaluation for all 16 sequences).  RK4 state lives in LDS.
+// Accepted: 0 < D <= 64, H <= 512, H % 64 == 0 (waves without a row tile idle) -- run at every such shape class by tests/test_latent_widths.py.
 // ---------------------------------------------------------------------------------------------
 #define LAT_NCOL 16
 
@@ -200,6 +201,7 @@ extern "C" int caspr_latent_rk4_f32(const float *z0, int ldz, const float *times
 // Three team barriers per evaluation (monotonic counter, release / acquire at agent scope, bounded spin).  All
 // workgroups carry the RK4 state redundantly (64 x 16 floats).  32 x ceil(B/16) workgroups must be co-resident: they are
 // tiny (256 threads) and 256 CUs are available; a team member that is not yet scheduled only delays the others.
+// Accepted: 0 < D <= 64, H == 512, B <= 64 (all three modes; xw = roundup4(D) in the training forms) -- run at D = 1 .. 64 by tests/test_latent_widths.py.
 // ---------------------------------------------------------------------------------------------
 #define LM_TEAM 32
 #define LM_SPIN_LIMIT (1u << 24)
@@ -281,8 +283,10 @@ __global__ __launch_bounds__(256) void latent_rk4_team_kernel(const float *__res
         st4(&sW2[i * 4], ld4(w2p + ((long)w * KCH) * 256 + i * 4));
     }
     {
-        const int mt = tid >> 6;   // 4 row tiles x 64 lanes
-        st4(&sW3[tid * 4], ld4(w3p + ((long)mt * KCH + w) * 256 + lane * 4));
+        // 4 row tiles x 64 lanes; the pack of a (D, 512) weight holds only ceil(D / 16) row tiles (caspr_packed_size): the
+        // tiles above them are not read (they would lie past the allocation) and stay zero -- their output rows d >= D are unused
+        const int mt = tid >> 6;
+        st4(&sW3[tid * 4], mt < (D + 15) / 16 ? ld4(w3p + ((long)mt * KCH + w) * 256 + lane * 4) : (f32x4){0.f, 0.f, 0.f, 0.f});
     }
     for (int i = tid; i < 64 * LAT_NCOL; i += 256) {
         const int d = i / LAT_NCOL, c = i % LAT_NCOL;

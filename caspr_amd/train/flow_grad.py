@@ -511,7 +511,7 @@ class LatentSolve(torch.autograd.Function):
         tape = []
 
         def f(z):
-            a = [z.contiguous()]
+            a = [_pad4(z)]                             # rows of roundup4(D) floats, zero-filled: conv1x1 takes row strides that are multiples of 4
             for i in range(4):
                 y = ops.conv1x1_train(pk[i], bd[i], a[-1].view(1, B, -1)).view(B, -1)[:, :ws[i].shape[0]]
                 a.append(torch.tanh(y) if i < 3 else y)
@@ -547,7 +547,7 @@ class LatentSolve(torch.autograd.Function):
 
         def fb(a, g):                              # a = (x, h1, h2, h3) of one evaluation, g = dL/d f(x) -> dL/dx
             for i in (3, 2, 1, 0):
-                d = g.contiguous() if i == 3 else torch.ops.aten.tanh_backward(g, a[i + 1])    # tanh' from the layer's stored output: one launch
+                d = _pad4(g) if i == 3 else torch.ops.aten.tanh_backward(g, a[i + 1])    # tanh' from the layer's stored output: one launch
                 deltas[i].append(d)
                 inputs[i].append(a[i])
                 g = ops.conv1x1_train(pkt[i], None, d.view(1, B, -1)).view(B, -1)[:, :ws[i].shape[1]]

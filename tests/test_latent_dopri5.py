@@ -19,6 +19,10 @@ f32 and in f64 (evaluations [74,68,74,68,62,80] against [74,68,68,68,80,80] on s
   * attempts whose s64 lies inside [1 - delta, 1 + delta] decide nothing: at most 10 % of the attempts of the matrix, which must also
     hold at least one rejected attempt.
 
+  * a second matrix (WIDTHS) holds the same criterion at the other widths the kernel accepts -- (D, H) = (20, 512), (33, 256), (64, 64),
+    (1, 64) on the nets of test_latent_widths.py -- with totals and a 10 % cap of its own; that its tolerance and horizon produce
+    rejected attempts is checked on the CPU, on the oracle's f32 run.
+
 Every figure lands in test_hip_parity's JSON report under "latent_dopri5:" keys.
 
 Three one-line mutations of csrc/ode_latent_dp5.hip, each of which makes this file fail (tried on the GPU: each breaks 10 of the 20
@@ -27,6 +31,7 @@ LDP_BETA's 44/45 -> 44/46; LDP_SAFETY 0.9 -> 0.8; the first mid-point weight of 
 """
 import math
 import os
+import types
 
 import numpy as np
 import pytest
@@ -35,10 +40,19 @@ import torch
 from oracle import model as O
 from test_hip_parity import REPORT, record
 from test_cnf_dopri5 import check_decisions, controller, initial_step, same_bits
+from test_latent_widths import module, net
 
 Z_TOL = 1e-5
 PRE = "latent_ode.ode_func.dynamics_net"
 BASE_STAMPS = [0.0, 0.0, 0.05, 0.1, 0.1, 0.35, 0.5, 0.8, 1.0]       # a stamp equal to times[0], a repeat, 0.05 / 0.1 inside the first steps
+# (D, H) next to the models' (64, 512), on the nets of test_latent_widths.py (non-zero biases on all four layers): a ragged K chunk of
+# layer 0 and RTD = 2 row tiles of the output layer; RTD = 3 and KCH = 16 < 32 chunks; seven of the eight waves without a row tile;
+# one component, so that the `/ D` of the error norms divides by 1
+WIDTHS = [(20, 512), (33, 256), (64, 64), (1, 64)]
+
+
+def width_name(D, H):
+    return "D%dH%d" % (D, H)
 
 
 def rnd(seed, *shape, scale=1.0):
@@ -46,10 +60,10 @@ def rnd(seed, *shape, scale=1.0):
     return torch.randn(*shape, generator=g) * scale
 
 
-def sequences(seed, B):
+def sequences(seed, B, D=64):
     """z0 = 0.5 .. 2.0 x randn, the scale cycling along the batch."""
     scales = torch.tensor([0.5, 0.8, 1.1, 1.4, 1.7, 2.0])[torch.arange(B) % 6]
-    return rnd(seed, B, 64) * scales[:, None]
+    return rnd(seed, B, D) * scales[:, None]
 
 
 def stamps(horizon, t_first=0.0, base=BASE_STAMPS):
@@ -293,6 +307,8 @@ def models(dev, seeded_sd, stress_sd):
         m = CaSPR(latent_method="dopri5")
         m.load_state_dict(sd)
         out[name] = (m.to(dev).eval(), sd)
+    for D, H in WIDTHS:                               # the other widths the kernel accepts: LatentODE(input_size = D, hidden_size = H) alone
+        out[width_name(D, H)] = (types.SimpleNamespace(latent_ode=module(D, H, dev, method="dopri5")), net(D, H))
     return out
 
 
@@ -360,14 +376,19 @@ def case_stamps(case, seed):
                                                                               "strided" if c["strided"] else "contig") for c in CASES])
 def test_route_matrix(dev, models, case):
     """State and decisions of the replayed sequences against the f64 replay of the kernel's own attempts; the launch twice, bit for bit."""
+    route_case(dev, models, case, MATRIX, len(CASES))
+
+
+def route_case(dev, models, case, MATRIX, ncases):
+    """One case of a route matrix (`MATRIX`: its running totals, `ncases` its length); D = case["D"] latent dims (64 where absent)."""
     model, sd = models[case["w"]]
-    B, tol = case["B"], case["tol"]
+    B, tol, D = case["B"], case["tol"], case.get("D", 64)
     seed = 3000 + 50 * B + case["Tu"]
-    z0 = sequences(seed, B)
+    z0 = sequences(seed, B, D)
     if case["strided"]:
         wide = torch.full((B, 1600), float("nan"))
-        wide[:, :64] = z0
-        zg = wide.to(dev)[:, :64]                    # the encoder's layout: a column slice, row stride 1600
+        wide[:, :D] = z0
+        zg = wide.to(dev)[:, :D]                     # the encoder's layout: a column slice, row stride 1600
     else:
         zg = z0.to(dev).contiguous()
     times, tt = case_stamps(case, seed + 1)
@@ -426,12 +447,59 @@ def test_route_matrix(dev, models, case):
     MATRIX["attempts"] += stats["attempts"]
     MATRIX["undecided"] += stats["undecided"]
     MATRIX["cases"] += 1
-    report("matrix:totals", attempts=MATRIX["attempts"], undecided=MATRIX["undecided"], rejected=MATRIX["rejected"],
+    report(MATRIX.get("key", "matrix:totals"), attempts=MATRIX["attempts"], undecided=MATRIX["undecided"], rejected=MATRIX["rejected"],
            worst_s32_minus_s64=MATRIX["worst_s_diff"], delta=4 * MATRIX["worst_s_diff"])
     assert MATRIX["undecided"] <= 0.1 * max(MATRIX["attempts"], 10), "attempts that decide nothing: %d of %d" % (MATRIX["undecided"], MATRIX["attempts"])
-    if MATRIX["cases"] == len(CASES):
+    if MATRIX["cases"] == ncases:
         assert MATRIX["rejected"] >= 1, "the matrix holds no rejected attempt: the reject path was not exercised"
     assert not bad, "\n".join(bad)
+
+
+def _width_cases():
+    """Per (D, H) of WIDTHS: five sequences at 1e-6 over a horizon of 3 (all replayed; strided z0, repeated stamps, times[0] = 0.25) and
+    seventeen at 1e-3 through solve_at (two workgroups, the second with one column)."""
+    out = []
+    for D, H in WIDTHS:
+        out.append(dict(D=D, H=H, w=width_name(D, H), B=5, Tu=9, tol=1e-6, horizon=3.0, pattern="repeats", strided=True, t_first=0.25))
+        out.append(dict(D=D, H=H, w=width_name(D, H), B=17, Tu=2, tol=1e-3, horizon=1.0, pattern="solve_at", strided=False, t_first=0.0))
+    return out
+
+
+WIDTH_CASES = _width_cases()
+WIDTH_MATRIX = dict(attempts=0, undecided=0, rejected=0, worst_s_diff=0.0, cases=0, key="matrix_widths:totals")
+WIDTH_IDS = ["D%d-H%d-b%d-tu%d-%.0e-h%d-%s-%s" % (c["D"], c["H"], c["B"], c["Tu"], c["tol"], c["horizon"], c["pattern"], "strided" if c["strided"] else "contig")
+             for c in WIDTH_CASES]
+
+
+def test_width_cases_hold_a_rejected_attempt():
+    """CPU: the oracle's f32 run on the width cases, in the kernel's place -- its attempts hold at least one rejection between them
+    (tolerance and horizon were chosen for that), and the GPU test's state and accept / reject checks pass on it."""
+    bad, stats, rejected = [], dict(attempts=0, undecided=0), 0
+    for case in WIDTH_CASES:
+        sd, B, tol = net(case["D"], case["H"]), case["B"], case["tol"]
+        seed = 3000 + 50 * B + case["Tu"]
+        z0 = sequences(seed, B, case["D"])
+        rel = rel_of(case_stamps(case, seed + 1)[0])
+        for b in (range(B) if B <= 5 else sorted({0, 7, 15, B - 1})):
+            p64, p32 = problem(sd, z0[b]), problem(sd, z0[b], torch.float32)
+            out32, _, ratios32, dts32 = oracle_run(*p32, rel, tol, tol)
+            acc32 = [x[0] <= 1 for x in ratios32]
+            rejected += acc32.count(False)
+            w, r64 = measure_delta(p32, p64, rel, tol, tol, dts32, acc32)
+            tag = "%s sequence %d" % (case["w"], b)
+            print("%s: %d attempts, %d rejected, s64 %s" % (tag, len(acc32), acc32.count(False), ["%.4f" % math.sqrt(r[0]) for r in r64["ratios"]]))
+            check_decisions(tag, r64, dict(accepted=acc32), 4 * w, bad, stats, controller_too=False)
+            check_state(tag, torch.cat(out32, 0), r64, bad)
+    assert rejected >= 1, "the width cases hold no rejected attempt"
+    assert stats["undecided"] <= 0.1 * stats["attempts"]
+    assert not bad, "\n".join(bad)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", WIDTH_CASES, ids=WIDTH_IDS)
+def test_route_matrix_widths(dev, models, case):
+    """The route matrix's criterion at the other widths the kernel accepts (WIDTHS), with its own totals and its own 10 % cap."""
+    route_case(dev, models, case, WIDTH_MATRIX, len(WIDTH_CASES))
 
 
 @pytest.mark.gpu
