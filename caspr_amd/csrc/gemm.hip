@@ -717,7 +717,11 @@ extern "C" int caspr_conv1x1_f32(const float *wp, const float *bias, const float
         CASPR_CHECK_LAUNCH("conv1x1(narrow)");
         return CASPR_OK;
     }
-    if (force == 7 || (force == 0 && P >= 128 && Cin >= 32 * ST_DB && !(act & CASPR_CONV_ROW_INVARIANT))) {
+    // The streaming kernel stages a fused call's scale / shift rows in sSS[2][GEMM_MAXC] with no global-memory alternative: wider
+    // fused inputs stay on the LDS-tiled kernel, which reads them from global memory there (ss_lds).
+    CASPR_REQUIRE(force != 7 || !in_scale || Cin <= GEMM_MAXC, "conv1x1: the streaming kernel takes a fused input of at most %d channels (Cin=%d)",
+                  GEMM_MAXC, Cin);
+    if (force == 7 || (force == 0 && P >= 128 && Cin >= 32 * ST_DB && (!in_scale || Cin <= GEMM_MAXC) && !(act & CASPR_CONV_ROW_INVARIANT))) {
         dim3 grid(ceil_div(Cout, GEMM_MT), ceil_div(P, 128), B);
         // The narrow variant (<= 16 outputs: the T-NOCS regression, a pure stream over 2.1 GB) is launched POLITE: 16 KB of unused dynamic LDS on
         // top of its 16 KB, so that at most five of its workgroups share a compute unit (it needs ~8 MB in flight to saturate HBM and has

@@ -175,9 +175,15 @@ int caspr_three_interp_add_gn_f32(const float *u, int ldu, const int32_t *idx, c
  *          row's data only -- not on P or on the row's position in the batch entry (same kernel, same K order for every
  *          row tile).  The hyper-network conv of the CNF runs over frames-as-rows with this flag so that a frame's gates do
  *          not change with the batch it is part of (sharding invariance).
- * Kernel choice inside (by shape only, never by B, so a batch ENTRY's result does not depend on the batch around it): P <= 16
- * rows per entry without a fused input transform -> one workgroup per (16 outputs, entry); Cout <= 16 -> streaming kernel with
- * one row tile per wave; P >= 128 and Cin >= 192 -> streaming kernel; otherwise the LDS-tiled kernel.  The guarantee is per
+ * Kernel choice inside (by shape only, never by B, so a batch ENTRY's result does not depend on the batch around it), first match:
+ *   1. P <= 16 rows per entry, no fused input transform, no CASPR_CONV_ROW_INVARIANT -> one workgroup per (16 outputs, entry);
+ *   2. P >= 128, Cin < 192, no fused input transform, no flag -> the narrow kernel: a wave holds the whole K extent of its 32 rows
+ *      in registers, 1 / 2 / 4 / 8 row tiles of 16 outputs per wave for Cout <= 16 / <= 32 / <= 64 / above;
+ *   3. P >= 128, Cin >= 192, no flag, and Cin <= 2048 if the input transform is fused (the kernel stages scale / shift in 2 x 2048
+ *      floats of LDS) -> the streaming kernel, with one row tile per wave if Cout <= 16 and eight otherwise;
+ *   4. otherwise the LDS-tiled kernel on 64-point tiles (128-point tiles only where ceil(P / 64) exceeds the grid's 65535): every
+ *      P < 128, every fused call with Cin < 192 or Cin > 2048, every call with the flag.
+ * P > 65535 * 128 is refused (split the call).  The guarantee is per
  * batch entry, NOT per row: without CASPR_CONV_ROW_INVARIANT a row's bits may depend on P (which kernel) and on its position
  * among the P rows (K order rotated by row tile).  Callers that put independent items along P and need them bitwise
  * independent of their neighbours (the hyper conv) set the flag; the training path's row products (train/flow_grad.py: all
