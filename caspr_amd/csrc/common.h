@@ -84,6 +84,23 @@ __device__ __forceinline__ float sigmoid_fast(float x)
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896341f));
 }
 
+// The flow's moving batch norm in evaluation mode (normalization.py:59-108) on component d of a point; p = [weight 3 | bias 3 |
+// running mean 3 | running var 3].  The CNF solve kernels apply it to their input and to their output.
+__device__ __forceinline__ float mbn_apply(const float *p, int d, int reverse, float v)
+{
+    const float w = p[d], bb = p[3 + d], mean = p[6 + d], var = p[9 + d];
+    if (reverse) return (v - bb) * expf(-w) * expf(0.5f * logf(var + 1e-4f)) + mean;   // normalization.py:92-94
+    return (v - mean) * expf(-0.5f * logf(var + 1e-4f)) * expf(w) + bb;                // normalization.py:70-74
+}
+// ... and the shift it gives the log-density of a point (normalization.py:103-108)
+__device__ __forceinline__ float mbn_shift_logp(const float *p, int reverse, float lp)
+{
+    float ld = 0.f;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) ld += -0.5f * logf(p[9 + d] + 1e-4f) + p[d];
+    return reverse ? lp + ld : lp - ld;
+}
+
 // ---------------------------------------------------------------------------------------------
 // All-reduce over W = 4 / 8 / 16 consecutive lanes (aligned groups inside one 16-lane DPP row) with DPP moves:
 // quad_perm [1,0,3,2] (xor 1), quad_perm [2,3,0,1] (xor 2), row_half_mirror (quads 0<->1, 2<->3), row_mirror

@@ -684,23 +684,14 @@ __global__ __launch_bounds__(CNF_NT, 2) void cnf_rk4_kernel(CnfArgs a)
     float lp = 0.f, lacc = 0.f;  // log-density state, owned by tid < PT (sd == 0)
     if (pvalid) {
         float v = a.y_in[((long)bt * a.n + spt) * 3 + sd];
-        if (a.mbn_in) {
-            const float w = a.mbn_in[sd], bb = a.mbn_in[3 + sd], mean = a.mbn_in[6 + sd], var = a.mbn_in[9 + sd];
-            if (a.reverse) v = (v - bb) * expf(-w) * expf(0.5f * logf(var + 1e-4f)) + mean;   // normalization.py:92-94
-            else v = (v - mean) * expf(-0.5f * logf(var + 1e-4f)) * expf(w) + bb;             // normalization.py:70-74
-        }
+        if (a.mbn_in) v = mbn_apply(a.mbn_in, sd, a.reverse, v);
         y = v;
         if (WITH_DIV) ev = a.e[((long)bt * a.n + spt) * 3 + sd];
     }
     if (WITH_DIV) {
         if (tid < PT && p0 + tid < a.n) {
             lp = a.logp_in ? a.logp_in[(long)bt * a.n + p0 + tid] : 0.f;
-            if (a.mbn_in) {
-                float ld = 0.f;
-#pragma unroll
-                for (int d = 0; d < 3; ++d) ld += -0.5f * logf(a.mbn_in[9 + d] + 1e-4f) + a.mbn_in[d];  // :103-108
-                lp = a.reverse ? lp + ld : lp - ld;
-            }
+            if (a.mbn_in) lp = mbn_shift_logp(a.mbn_in, a.reverse, lp);
         }
         // tangent seed e sits in the tangent columns of s_ys for the whole solve
         if (is_state) s_ys[(PT + scol) * 4 + sd] = ev;
@@ -895,20 +886,11 @@ __global__ __launch_bounds__(CNF_NT, 2) void cnf_rk4_kernel(CnfArgs a)
 
     if (pvalid) {
         float v = y;
-        if (a.mbn_out) {
-            const float w = a.mbn_out[sd], bb = a.mbn_out[3 + sd], mean = a.mbn_out[6 + sd], var = a.mbn_out[9 + sd];
-            if (a.reverse) v = (v - bb) * expf(-w) * expf(0.5f * logf(var + 1e-4f)) + mean;
-            else v = (v - mean) * expf(-0.5f * logf(var + 1e-4f)) * expf(w) + bb;
-        }
+        if (a.mbn_out) v = mbn_apply(a.mbn_out, sd, a.reverse, v);
         a.y_out[((long)bt * a.n + spt) * 3 + sd] = v;
     }
     if (WITH_DIV && tid < PT && p0 + tid < a.n) {
-        if (a.mbn_out) {
-            float ld = 0.f;
-#pragma unroll
-            for (int d = 0; d < 3; ++d) ld += -0.5f * logf(a.mbn_out[9 + d] + 1e-4f) + a.mbn_out[d];
-            lp = a.reverse ? lp + ld : lp - ld;
-        }
+        if (a.mbn_out) lp = mbn_shift_logp(a.mbn_out, a.reverse, lp);
         a.logp_out[(long)bt * a.n + p0 + tid] = lp;
     }
 }

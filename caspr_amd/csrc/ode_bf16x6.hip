@@ -53,21 +53,12 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_x6_kernel(CnfX6Args a)
     float lp = 0.f, lacc = 0.f;   // DIV: log-density state of point j, owned by lane (g = 3, j < 8)
     {
         float v = a.y_in[((long)bt * a.n + ccol) * 3 + sd];
-        if (a.mbn_in) {
-            const float w = a.mbn_in[sd], bb = a.mbn_in[3 + sd], mean = a.mbn_in[6 + sd], var = a.mbn_in[9 + sd];
-            if (a.reverse) v = (v - bb) * expf(-w) * expf(0.5f * logf(var + 1e-4f)) + mean;   // normalization.py:92-94
-            else v = (v - mean) * expf(-0.5f * logf(var + 1e-4f)) * expf(w) + bb;             // normalization.py:70-74
-        }
+        if (a.mbn_in) v = mbn_apply(a.mbn_in, sd, a.reverse, v);
         y = v;
         if (DIV) {
             if (tg0) y = a.e[((long)bt * a.n + ccol) * 3 + sd];     // tangent lanes carry e_d (constant over the solve) in the state register
             lp = a.logp_in ? a.logp_in[(long)bt * a.n + ccol] : 0.f;
-            if (a.mbn_in) {
-                float ld = 0.f;
-#pragma unroll
-                for (int d = 0; d < 3; ++d) ld += -0.5f * logf(a.mbn_in[9 + d] + 1e-4f) + a.mbn_in[d];   // normalization.py:103-108
-                lp = a.reverse ? lp + ld : lp - ld;
-            }
+            if (a.mbn_in) lp = mbn_shift_logp(a.mbn_in, a.reverse, lp);
         }
     }
 
@@ -106,21 +97,12 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_x6_kernel(CnfX6Args a)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the prefetch left in flight by the last layer pass
 
     if (DIV && cvalid && g0 == 3 && !tg0) {
-        if (a.mbn_out) {
-            float ld = 0.f;
-#pragma unroll
-            for (int d = 0; d < 3; ++d) ld += -0.5f * logf(a.mbn_out[9 + d] + 1e-4f) + a.mbn_out[d];
-            lp = a.reverse ? lp + ld : lp - ld;
-        }
+        if (a.mbn_out) lp = mbn_shift_logp(a.mbn_out, a.reverse, lp);
         a.logp_out[(long)bt * a.n + col] = lp;
     }
     if (cvalid && g0 < 3 && !tg0) {
         float v = y;
-        if (a.mbn_out) {
-            const float w = a.mbn_out[sd], bb = a.mbn_out[3 + sd], mean = a.mbn_out[6 + sd], var = a.mbn_out[9 + sd];
-            if (a.reverse) v = (v - bb) * expf(-w) * expf(0.5f * logf(var + 1e-4f)) + mean;
-            else v = (v - mean) * expf(-0.5f * logf(var + 1e-4f)) * expf(w) + bb;
-        }
+        if (a.mbn_out) v = mbn_apply(a.mbn_out, sd, a.reverse, v);
         a.y_out[((long)bt * a.n + col) * 3 + sd] = v;
     }
 }

@@ -1,7 +1,9 @@
 // ode_dp5_f16x3w.hip -- the point-CNF SAMPLING solve integrated to a TOLERANCE (adaptive Dormand-Prince 5(4), error control per frame)
 // on THREE f16 products per f32 product (config.cnf_dp5_split = "f16x3"): the launch protocol of ode_dp5.hip around the evaluation of
-// ode_f16x3w.hip.  The loop is a copy of ode_dp5.hip's; the evaluation is shared with ode_f16x3w.hip as text (ode_h3w.h,
-// ode_h3w_setup.inc, ode_h3w_ring.inc, ode_h3w_eval.inc); read their headers first, this one lists what is particular to the combination.
+// ode_f16x3w.hip.  The loop's shared pieces are ONE text with ode_dp5.hip (dp5.h: frame state, slot sum, publication, block
+// reduction, workspace and host driver; dp5_rules.h: the controller's rules; dp5_tables.inc: the tableau); the evaluation is shared
+// with ode_f16x3w.hip as text (ode_h3w.h, ode_h3w_setup.inc, ode_h3w_ring.inc, ode_h3w_eval.inc); read their headers first, this one
+// lists what is particular to the combination.
 //
 //  * evaluation: cnf_rk4_h3w_kernel's stage body -- 128 points per workgroup, a wave owns 32 points and all 512 units, layer
 //    1's 256 accumulators in the hand-managed accumulator file (the f16 planes kept there during layer 2), the 8-deep LDS-DMA weight
@@ -34,46 +36,15 @@
 #define XH_NO_FLUSH2 0
 #define XH_STAMP(i)
 #include "ode_h3w.h"
+#include "dp5.h"
 
-// ---- Dormand-Prince 5(4), Shampine's variant as torchdiffeq 0.0.1 dopri5.py: the tables of ode_dp5.hip.  Rows 0 and 1 are the two
-// evaluations of the initial-step selection (y0 itself; y0 + h0 f0), rows 2..7 the six new stages of an attempt (the last: y_new, FSAL).
-__constant__ float DPH_BETA[8][6] = {
-    {0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
-    {1.f, 0.f, 0.f, 0.f, 0.f, 0.f},
-    {(float)(1.0 / 5), 0.f, 0.f, 0.f, 0.f, 0.f},
-    {(float)(3.0 / 40), (float)(9.0 / 40), 0.f, 0.f, 0.f, 0.f},
-    {(float)(44.0 / 45), (float)(-56.0 / 15), (float)(32.0 / 9), 0.f, 0.f, 0.f},
-    {(float)(19372.0 / 6561), (float)(-25360.0 / 2187), (float)(64448.0 / 6561), (float)(-212.0 / 729), 0.f, 0.f},
-    {(float)(9017.0 / 3168), (float)(-355.0 / 33), (float)(46732.0 / 5247), (float)(49.0 / 176), (float)(-5103.0 / 18656), 0.f},
-    {(float)(35.0 / 384), 0.f, (float)(500.0 / 1113), (float)(125.0 / 192), (float)(-2187.0 / 6784), (float)(11.0 / 84)},
-};
-__constant__ double DPH_ALPHA[8] = {0.0, 1.0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0, 1.0};
-__constant__ float DPH_CERR[7] = {(float)(35.0 / 384 - 1951.0 / 21600), 0.f, (float)(500.0 / 1113 - 22642.0 / 50085), (float)(125.0 / 192 - 451.0 / 720),
-                                  (float)(-2187.0 / 6784 - -12231.0 / 42400), (float)(11.0 / 84 - 649.0 / 6300), (float)(-1.0 / 60.0)};
-__constant__ float DPH_CMID[7] = {(float)(6025192743.0 / 30085553152.0 / 2), 0.f, (float)(51252292925.0 / 65400821598.0 / 2),
-                                  (float)(-2691868925.0 / 45128329728.0 / 2), (float)(187940372067.0 / 1594534317056.0 / 2),
-                                  (float)(-1776094331.0 / 19743644256.0 / 2), (float)(11237099.0 / 235043384.0 / 2)};
-#define DPH_SAFETY 0.9f
-#define DPH_IFACTOR 10.0f
-#define DPH_DFACTOR 0.2f
+// the tableau (dp5_tables.inc), in this file's constant memory as DPH_BETA, DPH_ALPHA, DPH_CERR, DPH_CMID
+#define DP5_TAB(x) DPH_##x
+#include "dp5_tables.inc"
 
-#define DPH_TRACE_HEAD 8     // floats per frame before the attempt rows: d0, d1, d2, h0, first dt, 0, 0, 0
-#define DPH_TRACE_ROW 5      // per attempt: t, dt, ratio of x, 0 (the ratio of logp on the other route), accepted (1 / 0)
 #define DPH_LDS (XH_LDS + 16 * 8)
+#define DPH_PT_FLOATS 15     // carry-over floats of a point in the workspace (dp5.h: a slot per 128-point workgroup): 5 quantities x 3
 #define DPH_GUARD 2u         // the status word's bit of this kernel (cnf_rk4_h3w_kernel sets bit 0)
-// carry-over quantities of a point, each [3 components][n]
-#define DPH_Y 0
-#define DPH_F0 1
-#define DPH_YN 2
-#define DPH_K7 3
-#define DPH_YM 4
-
-struct Dp5H3Frame {          // a frame's controller state (Dp5Frame of ode_dp5.hip), written by its first workgroup, double-buffered by launch parity
-    double t;                // solver time (negated when the solve runs in reverse, as upstream)
-    float dt, h0, d0, d1, d2, dt0;
-    int done, nacc, nrej, nfe;
-    int pad[2];
-};
 
 struct CnfDp5H3Args {
     const float *y_in, *hyper, *tcol, *w0, *b0, *b1, *b2, *w3, *b3, *mbn_in, *mbn_out;
@@ -84,11 +55,11 @@ struct CnfDp5H3Args {
     int launch;                   // 0: f(t0, y0); 1: f(t0 + h0, y0 + h0 f0); L >= 2: decide attempt L - 3, run attempt L - 2
     int last;                     // the attempt budget is used up: decide only
     int max_attempts;
-    Dp5H3Frame *frames;           // [2][BT]
+    Dp5Frame *frames;             // [2][BT]
     double *part;                 // [2][BT][workgroups of a frame][4]: sum of squares, points the range guard caught, second sum (launch 0), 0
     float *pts;                   // [BT][5][3][n]
     int *running;                 // [launch]: frames that did not retire in that launch
-    float *trace;                 // [BT][DPH_TRACE_HEAD + DPH_TRACE_ROW * max_attempts]
+    float *trace;                 // [BT][DP5_TRACE_HEAD + DP5_TRACE_ROW * max_attempts]
     int *counters;                // [BT][4]: accepted, rejected, evaluations, finished (1; 3: retired by the range guard)
     unsigned *status;             // one word per solve, zeroed in front of launch 0: DPH_GUARD set <-> the range guard tripped
 };
@@ -103,39 +74,24 @@ __global__ __launch_bounds__(256, 1) void cnf_dp5_h3w_kernel(CnfDp5H3Args a)
     const int ccol = cvalid ? col : a.n - 1;
     // lanes l and l + 32 hold the same point: the lower one owns it (counts it in the norms, stores its carry-over and its output)
     const bool own = cvalid && lane0 < 32;
-    float *pp = a.pts + (long)bt * 15 * a.n + ccol;             // quantity q, component d at pp[q * qs + d * n]
+    float *pp = a.pts + (long)bt * DPH_PT_FLOATS * a.n + ccol;             // quantity q, component d at pp[q * qs + d * n]
     const long qs = 3L * a.n;
 
     const int Lc = a.launch, par = Lc & 1;
-    const Dp5H3Frame *fprev = a.frames + (long)(par ^ 1) * BT + bt;
-    Dp5H3Frame *fnext = a.frames + (long)par * BT + bt;
+    const Dp5Frame *fprev = a.frames + (long)(par ^ 1) * BT + bt;
+    Dp5Frame *fnext = a.frames + (long)par * BT + bt;
     const bool lead = blockIdx.x == 0 && tid == 0;
     const double sgn = a.reverse ? -1.0 : 1.0;
     const double tq1 = a.reverse ? 0.0 : (double)a.t_end;       // where the solve ends, in solver time
-    Dp5H3Frame st;
-    if (Lc > 0) {
-        st = *fprev;
-        if (st.done) {                                          // retired: carry the state over and leave
-            if (lead) *fnext = st;
-            return;
-        }
-    } else {
-        st.t = a.reverse ? -(double)a.t_end : 0.0;
-        st.dt = st.h0 = st.d0 = st.d1 = st.d2 = st.dt0 = 0.f;
-        st.done = st.nacc = st.nrej = st.nfe = 0;
-        st.pad[0] = st.pad[1] = 0;
-    }
+    Dp5Frame st;
+    DP5_FRAME_LOAD_OR_RETURN(st, fprev, fnext, Lc, lead, a.reverse, a.t_end);
 
     float s[3], f0[3] = {0.f, 0.f, 0.f};
     if (Lc == 0) {
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
             float v = a.y_in[((long)bt * a.n + ccol) * 3 + d];
-            if (a.mbn_in) {
-                const float w = a.mbn_in[d], bb = a.mbn_in[3 + d], mean = a.mbn_in[6 + d], var = a.mbn_in[9 + d];
-                if (a.reverse) v = (v - bb) * expf(-w) * expf(0.5f * logf(var + 1e-4f)) + mean;   // normalization.py:92-94
-                else v = (v - mean) * expf(-0.5f * logf(var + 1e-4f)) * expf(w) + bb;             // normalization.py:70-74
-            }
+            if (a.mbn_in) v = mbn_apply(a.mbn_in, d, a.reverse, v);
             s[d] = v;
         }
     } else {
@@ -145,21 +101,15 @@ __global__ __launch_bounds__(256, 1) void cnf_dp5_h3w_kernel(CnfDp5H3Args a)
         // owner alone computes; on accept every lane replaces them by y_new and k7, which this launch only reads.)
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
-            s[d] = pp[DPH_Y * qs + (long)d * a.n];
-            f0[d] = pp[DPH_F0 * qs + (long)d * a.n];
+            s[d] = pp[DP5_Y * qs + (long)d * a.n];
+            f0[d] = pp[DP5_F0 * qs + (long)d * a.n];
         }
     }
 
     // ---- the frame's sums of the previous launch: its workgroups' slots added in slot order, the same in every workgroup of the frame
-    double S[4] = {0.0, 0.0, 0.0, 0.0};
-    if (Lc > 0) {
-        const double *p = a.part + ((long)(par ^ 1) * BT + bt) * nwg * 4;
-        for (int w = 0; w < nwg; ++w)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) S[q] += p[4 * w + q];
-    }
+    DP5_SLOT_SUM(S, a.part, Lc, BT, bt, nwg)
     const double nx = 3.0 * (double)a.n;
-    float *trow = a.trace + (long)bt * (DPH_TRACE_HEAD + DPH_TRACE_ROW * a.max_attempts);
+    float *trow = a.trace + (long)bt * (DP5_TRACE_HEAD + DP5_TRACE_ROW * a.max_attempts);
     float dt = st.dt, hstep = 0.f;
     if (S[1] > 0.0) {
         // ---- the range guard caught a point of this frame in the previous launch: NaN in all of the frame's outputs, the frame retires
@@ -170,30 +120,27 @@ __global__ __launch_bounds__(256, 1) void cnf_dp5_h3w_kernel(CnfDp5H3Args a)
         }
         if (lead) {
             if (Lc >= 3) {                                      // the attempt that was to be decided: traced as rejected, ratio NaN
-                float *tr = trow + DPH_TRACE_HEAD + DPH_TRACE_ROW * (Lc - 3);
+                float *tr = trow + DP5_TRACE_HEAD + DP5_TRACE_ROW * (Lc - 3);
                 tr[0] = (float)(sgn * st.t); tr[1] = dt; tr[2] = __uint_as_float(0x7fc00000u); tr[3] = 0.f; tr[4] = 0.f;
                 ++st.nrej;
             }
             st.done = 1;
-            *fnext = st;
-            int *c = a.counters + 4 * bt;
-            c[0] = st.nacc; c[1] = st.nrej; c[2] = st.nfe; c[3] = 3;
+            DP5_PUBLISH(fnext, st, a.counters, bt, 3, false, a.running + Lc);
         }
         return;
     }
     if (Lc == 1) {
         // _select_initial_step: d0 = rms(y / scale), d1 = rms(f0 / scale)
         const double d0 = sqrt(S[0] / nx), d1 = sqrt(S[2] / nx);
-        const double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * (d0 / fmax(d1, 1e-300));
+        const double h0 = dp5_h0(d0, d1);
         st.d0 = (float)d0;
         st.d1 = (float)d1;
         st.h0 = (float)h0;
         hstep = st.h0;
     } else if (Lc == 2) {
         const float d2 = (float)(sqrt(S[0] / nx) / (double)st.h0);
-        const float h1 = (st.d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, st.h0 * 1e-3f) : powf(0.01f / fmaxf(st.d1, d2), 0.2f);
         st.d2 = d2;
-        dt = fminf(100.f * st.h0, h1);
+        dt = DP5_FIRST_DT(st.d1, d2, st.h0);
         st.dt0 = dt;
         if (lead) {
             trow[0] = st.d0; trow[1] = st.d1; trow[2] = d2; trow[3] = st.h0; trow[4] = dt; trow[5] = trow[6] = trow[7] = 0.f;
@@ -203,15 +150,9 @@ __global__ __launch_bounds__(256, 1) void cnf_dp5_h3w_kernel(CnfDp5H3Args a)
         // ---- decide attempt Lc - 3: ratio = mean((err / tol)^2), accept iff <= 1
         const float r = (float)(S[0] / nx);
         const bool accept = r <= 1.f;
-        float dt_next;
-        if (r == 0.f) dt_next = dt * DPH_IFACTOR;
-        else {
-            const float inv_d = r < 1.f ? 1.f : 1.f / DPH_DFACTOR;
-            const float factor = fmaxf(1.f / DPH_IFACTOR, fminf(powf(sqrtf(r), 0.2f) / DPH_SAFETY, inv_d));
-            dt_next = dt / factor;
-        }
+        const float dt_next = dp5_next_dt(r, dt);
         if (lead) {
-            float *tr = trow + DPH_TRACE_HEAD + DPH_TRACE_ROW * (Lc - 3);
+            float *tr = trow + DP5_TRACE_HEAD + DP5_TRACE_ROW * (Lc - 3);
             tr[0] = (float)(sgn * st.t); tr[1] = dt; tr[2] = r; tr[3] = 0.f; tr[4] = accept ? 1.f : 0.f;
         }
         if (accept) {
@@ -220,9 +161,9 @@ __global__ __launch_bounds__(256, 1) void cnf_dp5_h3w_kernel(CnfDp5H3Args a)
             float yn[3], k7[3], ym[3];
 #pragma unroll
             for (int d = 0; d < 3; ++d) {
-                yn[d] = pp[DPH_YN * qs + (long)d * a.n];
-                k7[d] = pp[DPH_K7 * qs + (long)d * a.n];
-                ym[d] = pp[DPH_YM * qs + (long)d * a.n];
+                yn[d] = pp[DP5_YN * qs + (long)d * a.n];
+                k7[d] = pp[DP5_K7 * qs + (long)d * a.n];
+                ym[d] = pp[DP5_YM * qs + (long)d * a.n];
             }
             if (t1s >= tq1) {
                 // ---- the step went past the end: the 4th-order interpolant at the end time (y_new itself when it lands on it)
@@ -231,20 +172,14 @@ __global__ __launch_bounds__(256, 1) void cnf_dp5_h3w_kernel(CnfDp5H3Args a)
                     for (int d = 0; d < 3; ++d) {
                         double v = (double)yn[d];
                         if (t1s != tq1) {
-                            const double y0d = s[d], y1d = yn[d], ymd = ym[d], fa = f0[d], fb = k7[d], h = dt;
-                            const double A = 2.0 * h * (fb - fa) - 8.0 * (y1d + y0d) + 16.0 * ymd;
-                            const double B = h * (5.0 * fa - 3.0 * fb) + 18.0 * y0d + 14.0 * y1d - 32.0 * ymd;
-                            const double C = h * (fb - 4.0 * fa) - 11.0 * y0d - 5.0 * y1d + 16.0 * ymd;
-                            const double D = h * fa;
+                            // (the text of dp5_interp / dp5_interp_at, dp5_rules.h: through the functions this kernel's register
+                            // allocation changes -- 488 of 512 VGPRs)
+                            DP5_INTERP_COEFS(s[d], yn[d], ym[d], f0[d], k7[d], dt)
                             const double xx = (tq1 - st.t) / (t1s - st.t);
-                            v = (((A * xx + B) * xx + C) * xx + D) * xx + y0d;
+                            v = DP5_INTERP_HORNER(xx);
                         }
                         float o = (float)v;
-                        if (a.mbn_out) {
-                            const float w = a.mbn_out[d], bb = a.mbn_out[3 + d], mean = a.mbn_out[6 + d], var = a.mbn_out[9 + d];
-                            if (a.reverse) o = (o - bb) * expf(-w) * expf(0.5f * logf(var + 1e-4f)) + mean;
-                            else o = (o - mean) * expf(-0.5f * logf(var + 1e-4f)) * expf(w) + bb;
-                        }
+                        if (a.mbn_out) o = mbn_apply(a.mbn_out, d, a.reverse, o);
                         a.y_out[((long)bt * a.n + col) * 3 + d] = o;
                     }
                 }
@@ -252,9 +187,7 @@ __global__ __launch_bounds__(256, 1) void cnf_dp5_h3w_kernel(CnfDp5H3Args a)
                     st.t = t1s;
                     st.dt = dt_next;
                     st.done = 1;
-                    *fnext = st;
-                    int *c = a.counters + 4 * bt;
-                    c[0] = st.nacc; c[1] = st.nrej; c[2] = st.nfe; c[3] = 1;
+                    DP5_PUBLISH(fnext, st, a.counters, bt, 1, false, a.running + Lc);
                 }
                 return;
             }
@@ -265,8 +198,8 @@ __global__ __launch_bounds__(256, 1) void cnf_dp5_h3w_kernel(CnfDp5H3Args a)
                 s[d] = yn[d];
                 f0[d] = k7[d];
                 if (own) {
-                    pp[DPH_Y * qs + (long)d * a.n] = s[d];
-                    pp[DPH_F0 * qs + (long)d * a.n] = f0[d];
+                    pp[DP5_Y * qs + (long)d * a.n] = s[d];
+                    pp[DP5_F0 * qs + (long)d * a.n] = f0[d];
                 }
             }
         } else {
@@ -277,10 +210,7 @@ __global__ __launch_bounds__(256, 1) void cnf_dp5_h3w_kernel(CnfDp5H3Args a)
         if (a.last) {
             if (lead) {
                 st.dt = dt;
-                *fnext = st;
-                int *c = a.counters + 4 * bt;
-                c[0] = st.nacc; c[1] = st.nrej; c[2] = st.nfe; c[3] = 0;
-                atomicAdd(a.running + Lc, 1);
+                DP5_PUBLISH(fnext, st, a.counters, bt, 0, true, a.running + Lc);
             }
             return;
         }
@@ -291,10 +221,7 @@ __global__ __launch_bounds__(256, 1) void cnf_dp5_h3w_kernel(CnfDp5H3Args a)
     if (lead) {
         st.dt = dt;
         st.nfe += nst;
-        *fnext = st;
-        int *c = a.counters + 4 * bt;
-        c[0] = st.nacc; c[1] = st.nrej; c[2] = st.nfe; c[3] = 0;
-        atomicAdd(a.running + Lc, 1);
+        DP5_PUBLISH(fnext, st, a.counters, bt, 0, true, a.running + Lc);
     }
 
     // ================= the evaluation of cnf_rk4_h3w_kernel (ode_f16x3w.hip), shared with it as text =================
@@ -374,8 +301,8 @@ __global__ __launch_bounds__(256, 1) void cnf_dp5_h3w_kernel(CnfDp5H3Args a)
                 const float q0 = s[d] / sc, q1 = k[1][d] / sc;
                 v[0] += (double)q0 * (double)q0;
                 v[2] += (double)q1 * (double)q1;
-                pp[DPH_Y * qs + (long)d * a.n] = s[d];
-                pp[DPH_F0 * qs + (long)d * a.n] = k[1][d];
+                pp[DP5_Y * qs + (long)d * a.n] = s[d];
+                pp[DP5_F0 * qs + (long)d * a.n] = k[1][d];
             }
         } else if (Lc == 1) {
 #pragma unroll
@@ -397,49 +324,16 @@ __global__ __launch_bounds__(256, 1) void cnf_dp5_h3w_kernel(CnfDp5H3Args a)
                 const float tol = a.atol + a.rtol * fmaxf(fabsf(s[d]), fabsf(ys[d]));
                 const float q0 = err / tol;
                 v[0] += (double)q0 * (double)q0;
-                pp[DPH_YN * qs + (long)d * a.n] = ys[d];
-                pp[DPH_K7 * qs + (long)d * a.n] = k[6][d];
-                pp[DPH_YM * qs + (long)d * a.n] = ym;
+                pp[DP5_YN * qs + (long)d * a.n] = ys[d];
+                pp[DP5_K7 * qs + (long)d * a.n] = k[6][d];
+                pp[DP5_YM * qs + (long)d * a.n] = ym;
             }
         }
     }
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-#pragma unroll
-        for (int o_ = 32; o_ > 0; o_ >>= 1) v[q] += __shfl_xor(v[q], o_);
-    }
-    if (lane0 == 0) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) s_red[4 * wave + q] = v[q];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double *slot = a.part + (((long)par * BT + bt) * nwg + blockIdx.x) * 4;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) slot[q] = ((s_red[q] + s_red[4 + q]) + s_red[8 + q]) + s_red[12 + q];
-        slot[3] = 0.0;
-    }
+    DP5_BLOCK_REDUCE(v, 3, s_red, a.part + (((long)par * BT + bt) * nwg + blockIdx.x) * 4, tid, lane0, wave);
 }
 
-static inline long dph_align(long b) { return (b + 255) & ~255L; }
-struct Dp5H3Layout { long frames, part, running, pts, total; };
-static Dp5H3Layout dph_layout(int BT, int n, int max_attempts)
-{
-    Dp5H3Layout l;
-    const long nwg = ceil_div(n, XH_PTS);
-    l.frames = 0;
-    l.part = dph_align(2L * BT * (long)sizeof(Dp5H3Frame));
-    l.running = l.part + dph_align(2L * BT * nwg * 4 * (long)sizeof(double));
-    l.pts = l.running + dph_align(((long)max_attempts + 3) * (long)sizeof(int));
-    l.total = l.pts + dph_align((long)BT * 15 * n * (long)sizeof(float));
-    return l;
-}
-
-extern "C" long caspr_cnf_dopri5_h3_ws_bytes(int BT, int n, int max_attempts)
-{
-    if (BT <= 0 || n <= 0 || max_attempts <= 0) return 0;
-    return dph_layout(BT, n, max_attempts).total;
-}
+extern "C" long caspr_cnf_dopri5_h3_ws_bytes(int BT, int n, int max_attempts) { return dp5_ws_bytes(BT, n, max_attempts, XH_PTS, DPH_PT_FLOATS); }
 
 extern "C" int caspr_cnf_dopri5_h3_f32(const float *y_in, const float *hyper, int ldh, const float *tcol, const float *w0,
                                        const float *b0, const void *w1h, const float *b1, const void *w2h, const float *b2,
@@ -447,27 +341,19 @@ extern "C" int caspr_cnf_dopri5_h3_f32(const float *y_in, const float *hyper, in
                                        int reverse, const float *mbn_in, const float *mbn_out, unsigned *status, float *y_out, int BT,
                                        int n, void *ws, long ws_bytes, float *trace, int32_t *counters, void *stream)
 {
-    CASPR_REQUIRE(y_in && hyper && tcol && w0 && b0 && w1h && b1 && w2h && b2 && w3 && b3 && y_out && ws && trace && counters && status, "cnf_dopri5_h3: null pointer");
-    CASPR_REQUIRE(H == XC_H, "cnf_dopri5_h3: hidden width %d unsupported (kernel is built for 512-512-512, flow.py:89)", H);
-    CASPR_REQUIRE(BT > 0 && BT <= 65535 && n > 0 && max_attempts > 0 && ldh >= 2 * (3 * H + 3), "cnf_dopri5_h3: bad sizes");
-    CASPR_REQUIRE(rtol > 0.f && atol > 0.f && t_end > 0.f && rtol < INFINITY && atol < INFINITY && t_end < INFINITY, "cnf_dopri5_h3: rtol, atol and t_end must be positive and finite");
-    CASPR_REQUIRE(((uintptr_t)w1h % 16) == 0 && ((uintptr_t)w2h % 16) == 0 && ((uintptr_t)w0 % 16) == 0 && ((uintptr_t)w3 % 16) == 0,
-                  "cnf_dopri5_h3: weights must be 16-byte aligned");
-    const Dp5H3Layout l = dph_layout(BT, n, max_attempts);
-    CASPR_REQUIRE(ws_bytes >= l.total && ((uintptr_t)ws % 256) == 0, "cnf_dopri5_h3: workspace of %ld bytes, 256-byte aligned, needed", l.total);
+    const int bad = dp5_check("cnf_dopri5_h3", y_in && hyper && tcol && w0 && b0 && w1h && b1 && w2h && b2 && w3 && b3 && y_out && ws && trace && counters && status,
+                              true, H, XC_H, BT, n, max_attempts, ldh, rtol, atol, t_end, w0, w1h, w2h, w3, ws, ws_bytes,
+                              dp5_ws_bytes(BT, n, max_attempts, XH_PTS, DPH_PT_FLOATS));
+    if (bad) return bad;
+    const Dp5Layout l = dp5_layout(BT, n, max_attempts, XH_PTS, DPH_PT_FLOATS);
     hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
-        caspr_set_error("cnf_dopri5_h3: the host loop reads the device after every attempt and cannot run under stream capture");
-        return CASPR_EUNSUP;
-    }
     CnfDp5H3Args a;
     a.y_in = y_in; a.hyper = hyper; a.tcol = tcol; a.w0 = w0; a.b0 = b0; a.b1 = b1; a.b2 = b2; a.w3 = w3; a.b3 = b3;
     a.mbn_in = mbn_in; a.mbn_out = mbn_out; a.w1x = (const unsigned char *)w1h; a.w2x = (const unsigned char *)w2h;
     a.y_out = y_out; a.ldh = ldh; a.n = n; a.reverse = reverse & 1; a.t_end = t_end; a.rtol = rtol; a.atol = atol;
     a.max_attempts = max_attempts;
     unsigned char *wsb = (unsigned char *)ws;
-    a.frames = (Dp5H3Frame *)(wsb + l.frames);
+    a.frames = (Dp5Frame *)(wsb + l.frames);
     a.part = (double *)(wsb + l.part);
     a.running = (int *)(wsb + l.running);
     a.pts = (float *)(wsb + l.pts);
@@ -475,43 +361,10 @@ extern "C" int caspr_cnf_dopri5_h3_f32(const float *y_in, const float *hyper, in
     a.counters = counters;
     a.status = status;
     static CasprLdsOptIn optin;
-    const hipError_t err = caspr_lds_opt_in(optin, (const void *)cnf_dp5_h3w_kernel, DPH_LDS);
-    if (err != hipSuccess) {
-        caspr_set_error("cnf_dopri5_h3: hipFuncSetAttribute failed: %s", hipGetErrorString(err));
-        return CASPR_ELAUNCH;
-    }
-    int *h_running = nullptr;
-    if (hipHostMalloc((void **)&h_running, sizeof(int), hipHostMallocDefault) != hipSuccess) {
-        caspr_set_error("cnf_dopri5_h3: hipHostMalloc failed");
-        return CASPR_ELAUNCH;
-    }
-    hipError_t he = hipMemsetAsync(a.running, 0, ((long)max_attempts + 3) * sizeof(int), st);
-    if (he == hipSuccess) he = hipMemsetAsync(trace, 0, (long)BT * (DPH_TRACE_HEAD + DPH_TRACE_ROW * (long)max_attempts) * sizeof(float), st);
-    if (he == hipSuccess) he = hipMemsetAsync(status, 0, sizeof(unsigned), st);
-    int running = 1, rc = CASPR_OK;
-    // launch L = 0, 1: initial-step selection; L >= 2: decide attempt L - 3, run attempt L - 2; L = max_attempts + 2 decides only
-    for (int L = 0; he == hipSuccess && L <= max_attempts + 2; ++L) {
-        a.launch = L;
-        a.last = L == max_attempts + 2;
-        cnf_dp5_h3w_kernel<<<dim3(ceil_div(n, XH_PTS), BT), dim3(256), DPH_LDS, st>>>(a);
-        he = hipGetLastError();
-        if (he != hipSuccess || L < 3) continue;       // no frame's attempt is decided before launch 3
-        // one small pinned read per attempt: the frames that launch L left running
-        he = hipMemcpyAsync(h_running, a.running + L, sizeof(int), hipMemcpyDeviceToHost, st);
-        if (he == hipSuccess) he = hipStreamSynchronize(st);
-        if (he != hipSuccess) break;
-        running = *h_running;
-        if (running == 0) break;
-    }
-    (void)hipHostFree(h_running);
-    if (he != hipSuccess) {
-        caspr_set_error("cnf_dopri5_h3: %s", hipGetErrorString(he));
-        return CASPR_ELAUNCH;
-    }
-    if (running != 0) {
-        caspr_set_error("cnf_dopri5_h3: %d of %d frames did not reach t_end within max_attempts = %d (rtol %g, atol %g)", running, BT, max_attempts,
-                        (double)rtol, (double)atol);
-        rc = CASPR_ENOCONV;
-    }
-    return rc;
+    return dp5_run("cnf_dopri5_h3", optin, (const void *)cnf_dp5_h3w_kernel, DPH_LDS, BT, max_attempts, rtol, atol, a.running, trace, status, st,
+                   [&](int L, bool last) {
+                       a.launch = L;
+                       a.last = last;
+                       cnf_dp5_h3w_kernel<<<dim3(ceil_div(n, XH_PTS), BT), dim3(256), DPH_LDS, st>>>(a);
+                   });
 }

@@ -71,11 +71,7 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
         float v = a.y_in[((long)bt * a.n + ccol) * 3 + d];
-        if (a.mbn_in) {
-            const float w = a.mbn_in[d], bb = a.mbn_in[3 + d], mean = a.mbn_in[6 + d], var = a.mbn_in[9 + d];
-            if (a.reverse) v = (v - bb) * expf(-w) * expf(0.5f * logf(var + 1e-4f)) + mean;   // normalization.py:92-94
-            else v = (v - mean) * expf(-0.5f * logf(var + 1e-4f)) * expf(w) + bb;             // normalization.py:70-74
-        }
+        if (a.mbn_in) v = mbn_apply(a.mbn_in, d, a.reverse, v);
         y[d] = v;
     }
 
@@ -136,11 +132,7 @@ __global__ __launch_bounds__(256, 1) void cnf_rk4_h3w_kernel(CnfH3Args a)
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
             float v = y[d];
-            if (a.mbn_out) {
-                const float w = a.mbn_out[d], bb = a.mbn_out[3 + d], mean = a.mbn_out[6 + d], var = a.mbn_out[9 + d];
-                if (a.reverse) v = (v - bb) * expf(-w) * expf(0.5f * logf(var + 1e-4f)) + mean;
-                else v = (v - mean) * expf(-0.5f * logf(var + 1e-4f)) * expf(w) + bb;
-            }
+            if (a.mbn_out) v = mbn_apply(a.mbn_out, d, a.reverse, v);
             a.y_out[((long)bt * a.n + col) * 3 + d] = bad ? __uint_as_float(0x7fc00000u) : v;
         }
     }

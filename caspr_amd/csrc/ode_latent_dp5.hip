@@ -22,36 +22,23 @@
 //    finished = 0 and NaN in the rows it did not reach.
 // No inter-workgroup communication, no co-residency requirement, no host read: the launch can be captured.
 // A sequence's output, trace and counters are bit-identical whichever column, workgroup or batch it sits in.
+// The controller's rules (next step, initial step, interpolant) are dp5_rules.h's and the tableau dp5_tables.inc's: one text with
+// the two point-CNF solves.
 #include <math.h>
 #include <stdlib.h>
 
 #include "common.h"
+#include "dp5_rules.h"
 
 #define LDP_NCOL 16
 #define LDP_EL (64 * LDP_NCOL)    // one state array: [d][c]
 #define LDP_TRACE_HEAD 8          // floats per sequence before the attempt rows: d0, d1, d2, h0, first dt, 0, 0, 0
 #define LDP_TRACE_ROW 4           // per attempt: t, dt, ratio, accepted (1 / 0)
 
-// ---- Dormand-Prince 5(4), Shampine's variant as torchdiffeq 0.0.1 dopri5.py.  Rows 0 and 1 are the two evaluations of the
-// initial-step selection (z0 itself; z0 + h0 f0), rows 2..7 the six new stages of an attempt (the last one is y_new: FSAL).
-__constant__ float LDP_BETA[8][6] = {
-    {0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
-    {1.f, 0.f, 0.f, 0.f, 0.f, 0.f},
-    {(float)(1.0 / 5), 0.f, 0.f, 0.f, 0.f, 0.f},
-    {(float)(3.0 / 40), (float)(9.0 / 40), 0.f, 0.f, 0.f, 0.f},
-    {(float)(44.0 / 45), (float)(-56.0 / 15), (float)(32.0 / 9), 0.f, 0.f, 0.f},
-    {(float)(19372.0 / 6561), (float)(-25360.0 / 2187), (float)(64448.0 / 6561), (float)(-212.0 / 729), 0.f, 0.f},
-    {(float)(9017.0 / 3168), (float)(-355.0 / 33), (float)(46732.0 / 5247), (float)(49.0 / 176), (float)(-5103.0 / 18656), 0.f},
-    {(float)(35.0 / 384), 0.f, (float)(500.0 / 1113), (float)(125.0 / 192), (float)(-2187.0 / 6784), (float)(11.0 / 84)},
-};
-__constant__ float LDP_CERR[7] = {(float)(35.0 / 384 - 1951.0 / 21600), 0.f, (float)(500.0 / 1113 - 22642.0 / 50085), (float)(125.0 / 192 - 451.0 / 720),
-                                  (float)(-2187.0 / 6784 - -12231.0 / 42400), (float)(11.0 / 84 - 649.0 / 6300), (float)(-1.0 / 60.0)};
-__constant__ float LDP_CMID[7] = {(float)(6025192743.0 / 30085553152.0 / 2), 0.f, (float)(51252292925.0 / 65400821598.0 / 2),
-                                  (float)(-2691868925.0 / 45128329728.0 / 2), (float)(187940372067.0 / 1594534317056.0 / 2),
-                                  (float)(-1776094331.0 / 19743644256.0 / 2), (float)(11237099.0 / 235043384.0 / 2)};
-#define LDP_SAFETY 0.9f
-#define LDP_IFACTOR 10.0f
-#define LDP_DFACTOR 0.2f
+// the tableau (dp5_tables.inc), in this file's constant memory as LDP_BETA, LDP_CERR, LDP_CMID (the dynamics do not read t: no stage times)
+#define DP5_TAB(x) LDP_##x
+#define DP5_TAB_NO_ALPHA
+#include "dp5_tables.inc"
 
 // out rows [16*rt0, 16*(rt0+nrt)) of W (packed, KC chunks) times the B-tile `in`; epilogue(rt, acc)   (lat_layer of ode.hip)
 template <int NRT, typename Epi>
@@ -200,9 +187,9 @@ __global__ __launch_bounds__(512) void latent_dp5_kernel(const float *__restrict
 #pragma unroll
     for (int cc = 0; cc < 2; ++cc) { valid[cc] = b0i + 2 * wave + cc < B; fin[cc] = !valid[cc]; }
 
-    // the stamps of column cc up to time t1 (inclusive) from the interpolant p(x) = (((A x + B) x + C) x + Dc) x + y0 of the
-    // step [t0, t1] (lin == false: every stamp takes y1 -- the rows at times[0])
-    auto emit = [&](int cc, double t0, double t1, bool lin, double A, double Bc, double C, double Dc, float y0, float y1) {
+    // the stamps of column cc up to time t1 (inclusive) from the interpolant p (dp5_rules.h) of the step [t0, t1] (lin == false:
+    // every stamp takes y1 -- the rows at times[0])
+    auto emit = [&](int cc, double t0, double t1, bool lin, const Dp5Interp &p, float y1) {
         float *orow = out + (long)(b0i + 2 * wave + cc) * Tu * D;
         int c1 = cur[cc];
         while (c1 < Tu) {                            // the stamps are ascending: the ones <= t1 are a prefix of the rest
@@ -216,10 +203,7 @@ __global__ __launch_bounds__(512) void latent_dp5_kernel(const float *__restrict
         for (int i = cur[cc]; i < c1; ++i) {
             const double tn = (double)(times[i] - t_first);     // latent_ode_model.py:58
             double v = (double)y1;
-            if (lin && tn != t1) {
-                const double xx = (tn - t0) / (t1 - t0);
-                v = (((A * xx + Bc) * xx + C) * xx + Dc) * xx + (double)y0;
-            }
+            if (lin && tn != t1) v = dp5_interp_at(p, (tn - t0) / (t1 - t0));
             if (dv) orow[(long)i * D + lane] = (float)v;
         }
         cur[cc] = c1;
@@ -236,7 +220,7 @@ __global__ __launch_bounds__(512) void latent_dp5_kernel(const float *__restrict
         const float a = z / sc, b = f0 / sc;
         const double S0 = ldp_wave_sum(dv ? (double)a * (double)a : 0.0), S1 = ldp_wave_sum(dv ? (double)b * (double)b : 0.0);
         const double d0 = sqrt(S0 / dD), d1 = sqrt(S1 / dD);
-        const double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * (d0 / fmax(d1, 1e-300));
+        const double h0 = dp5_h0(d0, d1);
         d0c[cc] = (float)d0;
         d1c[cc] = (float)d1;
         h0c[cc] = (float)h0;
@@ -254,8 +238,7 @@ __global__ __launch_bounds__(512) void latent_dp5_kernel(const float *__restrict
         const float a = (f1 - f0) / sc;
         const double S = ldp_wave_sum(dv ? (double)a * (double)a : 0.0);
         const float d2 = (float)(sqrt(S / dD) / (double)h0c[cc]);
-        const float h1 = (d1c[cc] <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0c[cc] * 1e-3f) : powf(0.01f / fmaxf(d1c[cc], d2), 0.2f);
-        dtc[cc] = fminf(100.f * h0c[cc], h1);
+        dtc[cc] = dp5_first_dt(d1c[cc], d2, h0c[cc]);
         if (trace && lane < LDP_TRACE_HEAD) {
             const float hd[LDP_TRACE_HEAD] = {d0c[cc], d1c[cc], d2, h0c[cc], dtc[cc], 0.f, 0.f, 0.f};
             float v = 0.f;
@@ -263,7 +246,7 @@ __global__ __launch_bounds__(512) void latent_dp5_kernel(const float *__restrict
             for (int q = 0; q < LDP_TRACE_HEAD; ++q) v = lane == q ? hd[q] : v;
             trace[(long)(b0i + c) * (LDP_TRACE_HEAD + LDP_TRACE_ROW * max_attempts) + lane] = v;
         }
-        emit(cc, 0.0, 0.0, false, 0.0, 0.0, 0.0, 0.0, z, z);          // the stamps equal to times[0]: z0
+        emit(cc, 0.0, 0.0, false, Dp5Interp{0.0, 0.0, 0.0, 0.0, (double)z}, z);   // the stamps equal to times[0]: z0
         fin[cc] = cur[cc] >= Tu;
         if (lane == 0) { s_dt[c] = fin[cc] ? 0.f : dtc[cc]; s_done[c] = fin[cc] ? 1 : 0; }
     }
@@ -305,13 +288,7 @@ __global__ __launch_bounds__(512) void latent_dp5_kernel(const float *__restrict
             const float qe = err / tol;
             const float r = (float)(ldp_wave_sum(dv ? (double)qe * (double)qe : 0.0) / dD);     // mean((err / tol)^2)
             const bool accept = r <= 1.f;
-            float dt_next;
-            if (r == 0.f) dt_next = dt * LDP_IFACTOR;
-            else {
-                const float inv_d = r < 1.f ? 1.f : 1.f / LDP_DFACTOR;
-                const float factor = fmaxf(1.f / LDP_IFACTOR, fminf(powf(sqrtf(r), 0.2f) / LDP_SAFETY, inv_d));
-                dt_next = dt / factor;
-            }
+            const float dt_next = dp5_next_dt(r, dt);
             if (trace && lane < LDP_TRACE_ROW) {
                 const float v = lane == 0 ? (float)tc[cc] : lane == 1 ? dt : lane == 2 ? r : (accept ? 1.f : 0.f);
                 trace[(long)(b0i + c) * (LDP_TRACE_HEAD + LDP_TRACE_ROW * max_attempts) + LDP_TRACE_HEAD + LDP_TRACE_ROW * att + lane] = v;
@@ -320,11 +297,7 @@ __global__ __launch_bounds__(512) void latent_dp5_kernel(const float *__restrict
                 ++nacc[cc];
                 const double t0 = tc[cc], t1 = tc[cc] + (double)dt;
                 const float ymid = z + dt * ms;
-                const double y0d = z, y1d = yn, ymd = ymid, fa = kk[0], fb = kk[6], h = dt;
-                const double A = 2.0 * h * (fb - fa) - 8.0 * (y1d + y0d) + 16.0 * ymd;
-                const double Bc = h * (5.0 * fa - 3.0 * fb) + 18.0 * y0d + 14.0 * y1d - 32.0 * ymd;
-                const double C = h * (fb - 4.0 * fa) - 11.0 * y0d - 5.0 * y1d + 16.0 * ymd;
-                emit(cc, t0, t1, true, A, Bc, C, h * fa, z, yn);
+                emit(cc, t0, t1, true, dp5_interp(z, yn, ymid, kk[0], kk[6], dt), yn);
                 tc[cc] = t1;
                 if (dv) { s_z[e] = yn; s_k[0][e] = kk[6]; }              // commit; FSAL
                 fin[cc] = cur[cc] >= Tu;

@@ -69,6 +69,28 @@ def test_the_stage_body_is_one_text_and_every_fragment_is_a_build_dependency():
     assert os.path.abspath(os.path.join(csrc, frag)) in shared and shared <= deps
 
 
+def test_each_controller_text_exists_once_and_every_shared_file_is_a_build_dependency():
+    """What the three adaptive solves share (dp5_tables.inc, dp5_rules.h, dp5.h; common.h: the moving batch norm): each marker of the
+    tableau, the step-size rule, the interpolant and the batch-norm transform occurs in exactly one file of csrc, the shared one."""
+    import glob
+    from caspr_amd.csrc import build
+    csrc = os.path.join(ROOT, "caspr_amd", "csrc")
+    text = {os.path.basename(p): open(p).read() for p in glob.glob(os.path.join(csrc, "*")) if p.endswith((".hip", ".h", ".inc"))}
+    where = lambda lit: sorted(f for f, t in text.items() if lit in t)
+    assert where("19372.0 / 6561") == ["dp5_tables.inc"]
+    assert where("6025192743.0") == ["dp5_tables.inc"]
+    assert where("powf(sqrtf(r), 0.2f)") == ["dp5_rules.h"]
+    assert where("18.0 * y0d") == ["dp5_rules.h"] and text["dp5_rules.h"].count("18.0 * y0d") == 1
+    assert where("expf(-0.5f * logf(") == ["common.h"]
+    for f in ("ode_dp5.hip", NEW, "ode_latent_dp5.hip"):
+        assert '#include "dp5_tables.inc"' in text[f], f
+        assert '#include "dp5_rules.h"' in text[f] or '#include "dp5.h"' in text[f], f
+    assert '#include "dp5_rules.h"' in text["dp5.h"]
+    deps = {os.path.abspath(p) for p in build.deps()}
+    for f in ("dp5_tables.inc", "dp5_rules.h", "dp5.h"):
+        assert os.path.abspath(os.path.join(csrc, f)) in deps, f
+
+
 def test_state_dict_key_surface_is_unchanged(monkeypatch):
     from caspr_amd import ops
     from caspr_amd.models import CaSPR
