@@ -10,6 +10,7 @@ leading-dimension is given; index tensors are int32.
 """
 import contextlib
 import ctypes
+import functools
 
 import torch
 
@@ -267,25 +268,27 @@ CONV_SPLIT = _cfg.conv_split         # "f16x3": the layers of the persistent 512
                                      # inference only; matmul_mode()["conv"] says "bf16x6" for both (the family), the timer keys stay what they are
 
 
+def _split_switch(name):
+    """The switch `name` of this module, validated where it is read (a run-time switch: a misspelt value must not select bf16x6 silently)."""
+    value = globals()[name]
+    if value not in ("bf16x6", "f16x3"):
+        raise ValueError("caspr_amd.ops.%s must be 'bf16x6' or 'f16x3', got %r" % (name, value))
+    return value
+
+
 def conv_split():
-    """CONV_SPLIT, validated where it is read (a run-time switch: a misspelt value must not select bf16x6 silently)."""
-    if CONV_SPLIT not in ("bf16x6", "f16x3"):
-        raise ValueError("caspr_amd.ops.CONV_SPLIT must be 'bf16x6' or 'f16x3', got %r" % (CONV_SPLIT,))
-    return CONV_SPLIT
+    """CONV_SPLIT, validated where it is read."""
+    return _split_switch("CONV_SPLIT")
 
 
 def cnf_dp5_split():
-    """CNF_DP5_SPLIT, validated where it is read (a run-time switch: a misspelt value must not select bf16x6 silently)."""
-    if CNF_DP5_SPLIT not in ("bf16x6", "f16x3"):
-        raise ValueError("caspr_amd.ops.CNF_DP5_SPLIT must be 'bf16x6' or 'f16x3', got %r" % (CNF_DP5_SPLIT,))
-    return CNF_DP5_SPLIT
+    """CNF_DP5_SPLIT, validated where it is read."""
+    return _split_switch("CNF_DP5_SPLIT")
 
 
 def cnf_split():
-    """CNF_SPLIT, validated where it is read: the attribute is a run-time switch, and a misspelt value must not select bf16x6 silently."""
-    if CNF_SPLIT not in ("bf16x6", "f16x3"):
-        raise ValueError("caspr_amd.ops.CNF_SPLIT must be 'bf16x6' or 'f16x3', got %r" % (CNF_SPLIT,))
-    return CNF_SPLIT
+    """CNF_SPLIT, validated where it is read."""
+    return _split_switch("CNF_SPLIT")
 
 
 _X6_MIN_CIN = 192     # below this the f32 LDS kernel is used anyway (set-abstraction / input layers)
@@ -591,15 +594,84 @@ def _conv_h3_launch(x):
         status.post()
 
 
-def _conv_h3w(split):
-    """Does a layer that takes the persistent 512-channel kernel run on its f16x3 form?  split: None = CONV_SPLIT; the training tier
-    passes "bf16x6" (conv1x1_train, conv1x1_gn(split=)): its forward, backward and tapes keep the bits they had."""
-    return (conv_split() if split is None else split) == "f16x3"
-
-
 def conv1x1_train(*args, **kwargs):
     """conv1x1 for the training tier (train/encoder_grad.py, train/flow_grad.py): always the bf16x6 / f32 kernels, whatever CONV_SPLIT says."""
     return conv1x1(*args, split="bf16x6", **kwargs)
+
+
+# The route table of the pointwise conv (DESIGN.md, "The pointwise conv's route table"): which kernel takes a layer, and the entry of
+# each route per kind of call.  A new form of a kernel is one row here and one branch of _conv_route.
+_CONV_ENTRY = {
+    "f32": {"conv": "caspr_conv1x1_f32"},
+    "x6": {"conv": "caspr_conv1x1_bf16x6_f32", "gn": "caspr_conv1x1_gn_bf16x6_f32", "pooled": "caspr_conv1x1_gn_pooled_bf16x6_f32"},
+    "x6w": {"conv": "caspr_conv1x1_x6w_f32", "gn": "caspr_conv1x1_x6w_f32", "pooled": "caspr_conv1x1_x6w_pooled_f32", "part": "caspr_conv1x1_x6w_part_f32"},
+    "h3w": {"conv": "caspr_conv1x1_h3w_f32", "gn": "caspr_conv1x1_h3w_f32", "pooled": "caspr_conv1x1_h3w_pooled_f32", "part": "caspr_conv1x1_h3w_part_f32"},
+}
+_CONV_WIDE = ("x6w", "h3w")                # the persistent 512-channel kernel's two forms
+_CONV_NO_GN = (0, None, None, 0.0, None, None, None, None, None, None, 0)      # a wide entry as a plain conv: G = 0, no statistics, no workspace
+
+
+def _conv_route(pw, B, P, in_relu_from=0, act=0, row_invariant=False, groups=None, split=None):
+    """The kernel that takes this call: "f32" | "x6" (256-channel bf16x6) | "x6w" | "h3w" (the 512-channel kernel on bf16x6 / f16x3), from
+    the weight's flags, the call's shape and flags and this module's switches, read now.  groups: None for a plain conv; conv1x1_gn's
+    group count otherwise, and then None comes back when no kernel takes conv and statistics in one pass.  split: None = CONV_SPLIT;
+    the training tier passes "bf16x6" (conv1x1_train, conv1x1_gn(split=)): its forward, backward and tapes keep the bits they had.
+    Four rules that read like accidents and are not:
+      1. an epilogue (act != 0) or row_invariant keeps a plain conv off the wide kernel, which has neither;
+      2. a GroupNorm call asks x6_gn_ok and C % groups before anything else: without them it is conv1x1 + gn_stats, whatever else holds;
+      3. ... and that conv1x1 asks again without groups, so a layer with x6w_ok but not x6_gn_ok (Cin = 32 under a lowered
+         _X6W_MIN_CIN) still lands on the wide kernel, as a plain conv (G = 0);
+      4. CONV_SPLIT is read here as it stands.  It is validated (conv_split()) only on calls with split=None that go on: by conv1x1 when
+         the wide kernel takes the call, by the GroupNorm paths -- all three, the 256-channel route included -- once their workspace is
+         sized.  conv1x1_gn_early_ok never validates."""
+    mfma = CONV_BF16X6 and P % 128 == 0 and in_relu_from % 8 == 0 and not row_invariant
+    if groups is not None and not (mfma and pw.x6_gn_ok and pw.cout % groups == 0):
+        return None
+    if mfma and CONV_X6W and pw.x6w_ok and act == 0 and _x6w_fills(pw, B, P):
+        return "h3w" if (CONV_SPLIT if split is None else split) == "f16x3" else "x6w"
+    if groups is not None or (mfma and pw.x6_ok):
+        return "x6"
+    return "f32"
+
+
+def _conv_ldx(who, pw, x):
+    ldx = _chk_rows(x)
+    if x.shape[2] < pw.cin and ldx < (pw.cin + 3) // 4 * 4:
+        raise ValueError("%s: input rows hold %d channels, weight needs %d" % (who, x.shape[2], pw.cin))
+    return ldx
+
+
+def _conv_head(pw, bias, bbias, x, ldx, in_scale, in_shift, in_relu, in_relu_from, y, ldy):
+    """The arguments every conv entry takes behind its packed weight(s)."""
+    B, P, _ = x.shape
+    return (_p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu), int(in_relu_from), _p(y), ldy, B, P, pw.cin, pw.cout)
+
+
+def _conv_wide_packs(route, pw):
+    """The (main, tail) pack of a wide route, None for the others.  A pack is BUILT on first use, by launches on the current stream: a
+    caller resolves it once, on its own stream, in front of its timer and of any stream switch -- a part queued on a side stream must
+    find it finished, and the first call of a layer must not time the pack kernels."""
+    return pw.xh() if route == "h3w" else pw.xw() if route == "x6w" else None
+
+
+def _conv_launch(route, kind, pw, packs, x, head, rest):
+    """The one launch site: entry _CONV_ENTRY[route][kind] on (the route's pack(s), head, rest[, the f16x3 status word], stream).
+    packs: what _conv_wide_packs gave the caller."""
+    name = _CONV_ENTRY[route][kind]
+    entry = getattr(_lib.load(), name)
+    if packs is None:
+        packs = (pw.x3(),) if route == "x6" else (pw.data,)
+    args = (*map(_p, packs), *head, *rest)
+    if route == "h3w":
+        with _conv_h3_launch(x) as word:
+            _lib.check(entry(*args, word, _stream()), name)
+    else:
+        _lib.check(entry(*args, _stream()), name)
+
+
+def _conv_timer(route, pw, x):
+    B, P, _ = x.shape
+    return "k:conv1x1_%s:%d:%d:%d" % ("f32" if route == "f32" else "bf16x6", pw.cin, pw.cout, B * P)
 
 
 def conv1x1(pw, bias, x, bbias=None, in_scale=None, in_shift=None, in_relu=False, in_relu_from=0, act=0, out=None, row_invariant=False, split=None):
@@ -609,36 +681,18 @@ def conv1x1(pw, bias, x, bbias=None, in_scale=None, in_shift=None, in_relu=False
     if row_invariant:
         act = act | CONV_ROW_INVARIANT
     _chk_f32(bias, bbias, in_scale, in_shift)
-    ldx = _chk_rows(x)
+    ldx = _conv_ldx("conv1x1", pw, x)
     B, P, _ = x.shape
-    if x.shape[2] < pw.cin and ldx < (pw.cin + 3) // 4 * 4:
-        raise ValueError("conv1x1: input rows hold %d channels, weight needs %d" % (x.shape[2], pw.cin))
     if out is None:
         out = torch.empty(B, P, (pw.cout + 3) // 4 * 4, device=x.device, dtype=torch.float32)
     ldy = _chk_rows(out)
-    if CONV_BF16X6 and CONV_X6W and pw.x6w_ok and P % 128 == 0 and not row_invariant and in_relu_from % 8 == 0 and act == 0 and _x6w_fills(pw, B, P):
-        if _conv_h3w(split):
-            main, tail = pw.xh()
-            with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, pw.cout, B * P), 2), _conv_h3_launch(x) as word:
-                _lib.check(_lib.load().caspr_conv1x1_h3w_f32(_p(main), _p(tail), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
-                                                             int(in_relu_from), _p(out), ldy, B, P, pw.cin, pw.cout, 0, None, None, 0.0, None, None, None,
-                                                             None, None, None, 0, word, _stream()), "caspr_conv1x1_h3w_f32")
-            return out
-        main, tail = pw.xw()
-        with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, pw.cout, B * P), 2):
-            _lib.check(_lib.load().caspr_conv1x1_x6w_f32(_p(main), _p(tail), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
-                                                         int(in_relu_from), _p(out), ldy, B, P, pw.cin, pw.cout, 0, None, None, 0.0, None, None, None,
-                                                         None, None, None, 0, _stream()), "caspr_conv1x1_x6w_f32")
-        return out
-    if CONV_BF16X6 and pw.x6_ok and P % 128 == 0 and not row_invariant and in_relu_from % 8 == 0:
-        with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, pw.cout, B * P), 2):
-            _lib.check(_lib.load().caspr_conv1x1_bf16x6_f32(_p(pw.x3()), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
-                                                            int(in_relu_from), _p(out), ldy, B, P, pw.cin, pw.cout, act, _stream()),
-                       "caspr_conv1x1_bf16x6_f32")
-        return out
-    with timed("k:conv1x1_f32:%d:%d:%d" % (pw.cin, pw.cout, B * P), 2):
-        _lib.check(_lib.load().caspr_conv1x1_f32(_p(pw.data), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
-                                                 int(in_relu_from), _p(out), ldy, B, P, pw.cin, pw.cout, act, _stream()), "caspr_conv1x1_f32")
+    route = _conv_route(pw, B, P, in_relu_from, act, row_invariant, None, split)
+    if route in _CONV_WIDE and split is None:
+        conv_split()
+    packs = _conv_wide_packs(route, pw)
+    with timed(_conv_timer(route, pw, x), 2):
+        _conv_launch(route, "conv", pw, packs, x, _conv_head(pw, bias, bbias, x, ldx, in_scale, in_shift, in_relu, in_relu_from, out, ldy),
+                     _CONV_NO_GN if route in _CONV_WIDE else (act,))
     return out
 
 
@@ -669,6 +723,27 @@ def gn_stats(y, C, gamma, beta, groups=16, eps=1e-5, want_max=False):
     return (scale, shift, pmax) if want_max else (scale, shift)
 
 
+def _conv_gn_buffers(pw, x, pool=1, moments=0, want_max=False, out=None, write=True):
+    """What a conv with GroupNorm statistics writes -> (y | None, ldy, scale, shift, mean, rstd, pmax, workspace): statistics per `pool`
+    batch entries, mean / rstd (`moments` = the group count) and pmax only when asked for."""
+    B, P, _ = x.shape
+    C, Bs, dev = pw.cout, B // pool, x.device
+    y = out
+    if y is None and write:
+        y = torch.empty(B, P, (C + 3) // 4 * 4, device=dev, dtype=torch.float32)
+    ldy = _chk_rows(y) if y is not None else 0
+    scale = torch.empty(Bs, C, device=dev, dtype=torch.float32)
+    shift = torch.empty(Bs, C, device=dev, dtype=torch.float32)
+    mean = torch.empty(Bs, moments, device=dev, dtype=torch.float32) if moments else None
+    rstd = torch.empty(Bs, moments, device=dev, dtype=torch.float32) if moments else None
+    pmax = torch.empty(Bs, C, device=dev, dtype=torch.float32) if want_max else None
+    return y, ldy, scale, shift, mean, rstd, pmax, _workspace(_lib.load().caspr_conv_gn_ws_bytes(B, P, C), dev)
+
+
+def _conv_gn_result(y, scale, shift, mean=None, rstd=None, pmax=None):
+    return (y, scale, shift) + (() if mean is None else (mean, rstd)) + (() if pmax is None else (pmax,))
+
+
 def conv1x1_gn(pw, bias, x, gamma, beta, groups=16, eps=1e-5, want_max=False, want_moments=False, write=True, bbias=None,
                in_scale=None, in_shift=None, in_relu=False, in_relu_from=0, out=None, pool=1, split=None):
     """conv1x1 followed by the statistics of the GroupNorm on its output (the model's conv -> GroupNorm -> ReLU block):
@@ -682,113 +757,43 @@ def conv1x1_gn(pw, bias, x, gamma, beta, groups=16, eps=1e-5, want_max=False, wa
     # in_shift / bbias stay per entry (caspr_conv1x1_gn_pooled_bf16x6_f32)
     if pool < 1 or B % pool:
         raise ValueError("conv1x1_gn: pool=%d must divide the %d batch entries" % (pool, B))
-    if not (CONV_BF16X6 and pw.x6_gn_ok and P % 128 == 0 and C % groups == 0 and in_relu_from % 8 == 0):
+    route = _conv_route(pw, B, P, in_relu_from, groups=groups, split=split)
+    if route is None:
         y = conv1x1(pw, bias, x, bbias=bbias, in_scale=in_scale, in_shift=in_shift, in_relu=in_relu, in_relu_from=in_relu_from, out=out, split=split)
         yg = y.view(B // pool, pool * P, y.shape[2]) if pool > 1 else y
         if want_moments:
             from . import train_ops
             return (y,) + tuple(train_ops.gn_stats_train(yg, C, gamma, beta, groups, eps, want_max))
         return (y,) + tuple(gn_stats(yg, C, gamma, beta, groups, eps, want_max))
-    ldx = _chk_rows(x)
-    if x.shape[2] < pw.cin and ldx < (pw.cin + 3) // 4 * 4:
-        raise ValueError("conv1x1_gn: input rows hold %d channels, weight needs %d" % (x.shape[2], pw.cin))
-    dev = x.device
-    y = None
-    if write or out is not None:
-        y = out if out is not None else torch.empty(B, P, (C + 3) // 4 * 4, device=dev, dtype=torch.float32)
-    ldy = _chk_rows(y) if y is not None else 0
-    Bs = B // pool
-    scale = torch.empty(Bs, C, device=dev, dtype=torch.float32)
-    shift = torch.empty(Bs, C, device=dev, dtype=torch.float32)
-    mean = torch.empty(Bs, groups, device=dev, dtype=torch.float32) if want_moments else None
-    rstd = torch.empty(Bs, groups, device=dev, dtype=torch.float32) if want_moments else None
-    pmax = torch.empty(Bs, C, device=dev, dtype=torch.float32) if want_max else None
-    L = _lib.load()
-    ws = _workspace(L.caspr_conv_gn_ws_bytes(B, P, C), dev)
-    h3w = _conv_h3w(split)
-    if pool > 1 and CONV_X6W and pw.x6w_ok and _x6w_fills(pw, B, P) and h3w:
-        main, tail = pw.xh()
-        with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, C, B * P), 2), _conv_h3_launch(x) as word:
-            _lib.check(L.caspr_conv1x1_h3w_pooled_f32(_p(main), _p(tail), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
-                                                      int(in_relu_from), _p(y), ldy, B, P, pw.cin, C, groups, int(pool), _p(gamma), _p(beta), float(eps),
-                                                      _p(scale), _p(shift), _p(pmax), _p(mean), _p(rstd), _p(ws), ws.numel(), word, _stream()),
-                       "caspr_conv1x1_h3w_pooled_f32")
-        res = (y, scale, shift)
-        if want_moments:
-            res += (mean, rstd)
-        if want_max:
-            res += (pmax,)
-        return res
-    if pool > 1 and CONV_X6W and pw.x6w_ok and _x6w_fills(pw, B, P):
-        main, tail = pw.xw()
-        with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, C, B * P), 2):
-            _lib.check(L.caspr_conv1x1_x6w_pooled_f32(_p(main), _p(tail), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
-                                                      int(in_relu_from), _p(y), ldy, B, P, pw.cin, C, groups, int(pool), _p(gamma), _p(beta), float(eps),
-                                                      _p(scale), _p(shift), _p(pmax), _p(mean), _p(rstd), _p(ws), ws.numel(), _stream()),
-                       "caspr_conv1x1_x6w_pooled_f32")
-        res = (y, scale, shift)
-        if want_moments:
-            res += (mean, rstd)
-        if want_max:
-            res += (pmax,)
-        return res
-    if pool > 1:
-        with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, C, B * P), 2):
-            _lib.check(L.caspr_conv1x1_gn_pooled_bf16x6_f32(_p(pw.x3()), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
-                                                            int(in_relu_from), _p(y), ldy, B, P, pw.cin, C, groups, int(pool), _p(gamma), _p(beta),
-                                                            float(eps), _p(scale), _p(shift), _p(pmax), _p(mean), _p(rstd), _p(ws), ws.numel(),
-                                                            _stream()), "caspr_conv1x1_gn_pooled_bf16x6_f32")
-        res = (y, scale, shift)
-        if want_moments:
-            res += (mean, rstd)
-        if want_max:
-            res += (pmax,)
-        return res
-    if CONV_X6W and pw.x6w_ok and _x6w_fills(pw, B, P) and h3w:
-        main, tail = pw.xh()
-        with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, C, B * P), 2), _conv_h3_launch(x) as word:
-            _lib.check(L.caspr_conv1x1_h3w_f32(_p(main), _p(tail), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
-                                               int(in_relu_from), _p(y), ldy, B, P, pw.cin, C, groups, _p(gamma), _p(beta), float(eps),
-                                               _p(scale), _p(shift), _p(pmax), _p(mean), _p(rstd), _p(ws), ws.numel(), word, _stream()),
-                       "caspr_conv1x1_h3w_f32")
-        res = (y, scale, shift)
-        if want_moments:
-            res += (mean, rstd)
-        if want_max:
-            res += (pmax,)
-        return res
-    if CONV_X6W and pw.x6w_ok and _x6w_fills(pw, B, P):
-        main, tail = pw.xw()
-        with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, C, B * P), 2):
-            _lib.check(L.caspr_conv1x1_x6w_f32(_p(main), _p(tail), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
-                                               int(in_relu_from), _p(y), ldy, B, P, pw.cin, C, groups, _p(gamma), _p(beta), float(eps),
-                                               _p(scale), _p(shift), _p(pmax), _p(mean), _p(rstd), _p(ws), ws.numel(), _stream()),
-                       "caspr_conv1x1_x6w_f32")
-        res = (y, scale, shift)
-        if want_moments:
-            res += (mean, rstd)
-        if want_max:
-            res += (pmax,)
-        return res
-    with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, C, B * P), 2):     # conv + statistics epilogue + the finalize kernel
-        _lib.check(L.caspr_conv1x1_gn_bf16x6_f32(_p(pw.x3()), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
-                                                 int(in_relu_from), _p(y), ldy, B, P, pw.cin, C, groups, _p(gamma), _p(beta), float(eps),
-                                                 _p(scale), _p(shift), _p(pmax), _p(mean), _p(rstd), _p(ws), ws.numel(), _stream()),
-                   "caspr_conv1x1_gn_bf16x6_f32")
-    res = (y, scale, shift)
-    if want_moments:
-        res += (mean, rstd)
-    if want_max:
-        res += (pmax,)
-    return res
+    ldx = _conv_ldx("conv1x1_gn", pw, x)
+    y, ldy, scale, shift, mean, rstd, pmax, ws = _conv_gn_buffers(pw, x, pool, groups if want_moments else 0, want_max, out, write)
+    if split is None:
+        conv_split()
+    packs = _conv_wide_packs(route, pw)
+    with timed(_conv_timer(route, pw, x), 2):           # conv + statistics epilogue + the finalize kernel
+        _conv_launch(route, "pooled" if pool > 1 else "gn", pw, packs, x, _conv_head(pw, bias, bbias, x, ldx, in_scale, in_shift, in_relu, in_relu_from, y, ldy),
+                     (groups,) + ((int(pool),) if pool > 1 else ()) + (_p(gamma), _p(beta), float(eps), _p(scale), _p(shift), _p(pmax), _p(mean), _p(rstd),
+                                                                       _p(ws), ws.numel()))
+    return _conv_gn_result(y, scale, shift, mean, rstd, pmax)
+
+
+def _conv_part(route, pw, packs, x, head, ws, mt0, mt1, with_tail, reserve):
+    """Channel tiles [mt0, mt1) of a layer on the 512-channel kernel, with or without the < 512-channel remainder, partial statistics into ws;
+    all but `reserve` compute units."""
+    _conv_launch(route, "part", pw, packs, x, head, (mt0, mt1, int(with_tail), int(reserve), _p(ws), ws.numel()))
+
+
+def _conv_gn_finalize(ws, x, C, groups, pool, gamma, beta, eps, scale, shift, pmax, g0, g1):
+    """The statistics of GroupNorm groups [g0, g1) from the partials the parts left in ws."""
+    _lib.check(_lib.load().caspr_conv_gn_finalize_f32(_p(ws), ws.numel(), x.shape[0], x.shape[1], C, groups, g0, g1, int(pool), _p(gamma), _p(beta),
+                                                      float(eps), _p(scale), _p(shift), _p(pmax), None, None, _stream()), "caspr_conv_gn_finalize_f32")
 
 
 def conv1x1_gn_early_ok(pw, B, P, groups, early_channels):
     """Can conv1x1_gn_early run this layer in pieces?  The 512-channel kernel must take it, in at least two channel tiles, and the
     channels the caller wants early must lie inside GroupNorm group 0, inside the first tile."""
     C = pw.cout
-    return bool(CONV_BF16X6 and CONV_X6W and pw.x6w_ok and P % 128 == 0 and _x6w_fills(pw, B, P) and C % groups == 0 and C // 512 >= 2
-                and early_channels <= min(C // groups, 512))
+    return bool(_conv_route(pw, B, P) in _CONV_WIDE and C % groups == 0 and C // 512 >= 2 and early_channels <= min(C // groups, 512))
 
 
 def conv1x1_gn_early(pw, bias, x, gamma, beta, on_early, groups=16, eps=1e-5, in_scale=None, in_shift=None, in_relu=False, in_relu_from=0,
@@ -808,37 +813,18 @@ def conv1x1_gn_early(pw, bias, x, gamma, beta, on_early, groups=16, eps=1e-5, in
     if not conv1x1_gn_early_ok(pw, B, P, groups, 1):
         raise ValueError("conv1x1_gn_early: this layer does not run on the 512-channel kernel in >= 2 channel tiles")
     ldx = _chk_rows(x)
-    dev = x.device
-    y = torch.empty(B, P, (C + 3) // 4 * 4, device=dev, dtype=torch.float32)
-    ldy = _chk_rows(y)
-    scale = torch.empty(B, C, device=dev, dtype=torch.float32)
-    shift = torch.empty(B, C, device=dev, dtype=torch.float32)
-    pmax = torch.empty(B, C, device=dev, dtype=torch.float32)
-    L = _lib.load()
-    ws = _workspace(L.caspr_conv_gn_ws_bytes(B, P, C), dev)
-    h3w = _conv_h3w(None)
-    main, tail = pw.xh() if h3w else pw.xw()
+    y, ldy, scale, shift, _, _, pmax, ws = _conv_gn_buffers(pw, x, want_max=True)
+    conv_split()
+    route = _conv_route(pw, B, P)
+    part = functools.partial(_conv_part, route, pw, _conv_wide_packs(route, pw), x,
+                             _conv_head(pw, bias, None, x, ldx, in_scale, in_shift, in_relu, in_relu_from, y, ldy), ws)
+    finalize = functools.partial(_conv_gn_finalize, ws, x, C, groups, 1, gamma, beta, eps, scale, shift, pmax)
     mt_all = C // 512
-
-    def part(mt0, mt1, with_tail, reserve):
-        if h3w:
-            with _conv_h3_launch(x) as word:
-                _lib.check(L.caspr_conv1x1_h3w_part_f32(_p(main), _p(tail), _p(bias), None, _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
-                                                        int(in_relu_from), _p(y), ldy, B, P, pw.cin, C, mt0, mt1, int(with_tail), int(reserve), _p(ws),
-                                                        ws.numel(), word, _stream()), "caspr_conv1x1_h3w_part_f32")
-            return
-        _lib.check(L.caspr_conv1x1_x6w_part_f32(_p(main), _p(tail), _p(bias), None, _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu), int(in_relu_from),
-                                                _p(y), ldy, B, P, pw.cin, C, mt0, mt1, int(with_tail), int(reserve), _p(ws), ws.numel(), _stream()),
-                   "caspr_conv1x1_x6w_part_f32")
-
-    def finalize(g0, g1):
-        _lib.check(L.caspr_conv_gn_finalize_f32(_p(ws), ws.numel(), B, P, C, groups, g0, g1, 1, _p(gamma), _p(beta), float(eps), _p(scale), _p(shift),
-                                                _p(pmax), None, None, _stream()), "caspr_conv_gn_finalize_f32")
-    with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, C, B * P), 2):
+    with timed(_conv_timer(route, pw, x), 2):
         part(0, 1, False, 0)
         finalize(0, 1)
         on_early(pmax)
-        if tail_stream is not None and tail is not None and reserve_cus > 0:
+        if tail_stream is not None and C % 512 and reserve_cus > 0:
             main_stream = torch.cuda.current_stream()
             issued = torch.cuda.Event()
             issued.record(main_stream)               # the remainder reads x and writes its own columns of y / of the partials: nothing of tile 0's
@@ -867,49 +853,30 @@ def conv1x1_gn_tail_beside(pw, bias, x, gamma, beta, tail_stream, groups=16, eps
     take that kernel.  -> (y, scale, shift)."""
     B, P, _ = x.shape
     C = pw.cout
-    ok = (tail_stream is not None and CONV_BF16X6 and CONV_X6W and pw.x6w_ok and pw.x6_gn_ok and P % 128 == 0 and C % groups == 0 and in_relu_from % 8 == 0
-          and C % 512 != 0 and C > 512 and B % pool == 0 and _x6w_fills(pw, B, P) and not torch.cuda.is_current_stream_capturing())
-    if not ok:
+    if not (tail_stream is not None and (route := _conv_route(pw, B, P, in_relu_from, groups=groups)) in _CONV_WIDE and C % 512 != 0 and C > 512
+            and B % pool == 0 and not torch.cuda.is_current_stream_capturing()):
         return conv1x1_gn(pw, bias, x, gamma, beta, groups, eps, bbias=bbias, in_scale=in_scale, in_shift=in_shift, in_relu=in_relu,
                           in_relu_from=in_relu_from, pool=pool)
     _chk_f32(bias, bbias, in_scale, in_shift, gamma, beta)
     ldx = _chk_rows(x)
-    dev = x.device
-    y = torch.empty(B, P, (C + 3) // 4 * 4, device=dev, dtype=torch.float32)
-    ldy = _chk_rows(y)
-    Bs = B // pool
-    scale = torch.empty(Bs, C, device=dev, dtype=torch.float32)
-    shift = torch.empty(Bs, C, device=dev, dtype=torch.float32)
-    L = _lib.load()
-    ws = _workspace(L.caspr_conv_gn_ws_bytes(B, P, C), dev)
-    h3w = _conv_h3w(None)
-    main, tail = pw.xh() if h3w else pw.xw()
+    y, ldy, scale, shift, _, _, _, ws = _conv_gn_buffers(pw, x, pool)
+    conv_split()
+    part = functools.partial(_conv_part, route, pw, _conv_wide_packs(route, pw), x,
+                             _conv_head(pw, bias, bbias, x, ldx, in_scale, in_shift, in_relu, in_relu_from, y, ldy), ws)
     mt_all = C // 512
-
-    def part(mt0, mt1, with_tail):
-        if h3w:
-            with _conv_h3_launch(x) as word:
-                _lib.check(L.caspr_conv1x1_h3w_part_f32(_p(main), _p(tail), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu),
-                                                        int(in_relu_from), _p(y), ldy, B, P, pw.cin, C, mt0, mt1, int(with_tail), 0, _p(ws), ws.numel(),
-                                                        word, _stream()), "caspr_conv1x1_h3w_part_f32")
-            return
-        _lib.check(L.caspr_conv1x1_x6w_part_f32(_p(main), _p(tail), _p(bias), _p(bbias), _p(x), ldx, _p(in_scale), _p(in_shift), int(in_relu), int(in_relu_from),
-                                                _p(y), ldy, B, P, pw.cin, C, mt0, mt1, int(with_tail), 0, _p(ws), ws.numel(), _stream()),
-                   "caspr_conv1x1_x6w_part_f32")
-    with timed("k:conv1x1_bf16x6:%d:%d:%d" % (pw.cin, C, B * P), 2):
+    with timed(_conv_timer(route, pw, x), 2):
         main_stream = torch.cuda.current_stream()
         tail_stream.wait_stream(main_stream)
         with torch.cuda.stream(tail_stream):
-            part(mt_all, mt_all, True)               # the remainder only: its own columns of y and of the partials
+            part(mt_all, mt_all, True, 0)            # the remainder only: its own columns of y and of the partials
             tail_done = torch.cuda.Event()
             tail_done.record(tail_stream)
-        part(0, mt_all, False)
+        part(0, mt_all, False, 0)
         main_stream.wait_event(tail_done)
         for t_ in (x, y, ws, in_scale, in_shift, bbias, bias):
             if t_ is not None:
                 t_.record_stream(tail_stream)
-        _lib.check(L.caspr_conv_gn_finalize_f32(_p(ws), ws.numel(), B, P, C, groups, 0, groups, int(pool), _p(gamma), _p(beta), float(eps), _p(scale), _p(shift),
-                                                None, None, None, _stream()), "caspr_conv_gn_finalize_f32")
+        _conv_gn_finalize(ws, x, C, groups, pool, gamma, beta, eps, scale, shift, None, 0, groups)
     return y, scale, shift
 
 
