@@ -153,6 +153,19 @@ def _first_passing(diff_of, candidates, tol, refine=True, max_tries=3):
     return chosen, diffs
 
 
+def _check_pilot_options(cnf_steps_max, cnf_steps_safety, cnf_steps_points, cnf_steps_tol):
+    """What the per-frame step pilot (ops.cnf_frame_steps) needs of its four options: checked by the constructor for cnf_steps="frame" and
+    at the call by decode(differentiable=True, frame_steps="pilot"), which a model built with cnf_steps="uniform" may make too."""
+    if not (isinstance(cnf_steps_max, int) and 2 <= cnf_steps_max <= 256 and cnf_steps_max & (cnf_steps_max - 1) == 0):
+        raise ValueError("cnf_steps_max must be a power of two in 2..256, got %r" % (cnf_steps_max,))
+    if not (1.0 <= float(cnf_steps_safety) < float("inf")):
+        raise ValueError("cnf_steps_safety must be finite and >= 1, got %r" % (cnf_steps_safety,))
+    if int(cnf_steps_points) < 1:
+        raise ValueError("cnf_steps_points must be positive, got %r" % (cnf_steps_points,))
+    if cnf_steps_tol is not None and not (0.0 < float(cnf_steps_tol) < float("inf")):
+        raise ValueError("cnf_steps_tol must be positive and finite, got %r" % (cnf_steps_tol,))
+
+
 class CaSPR(nn.Module):
     # class-level defaults: a model pickled before these attributes existed keeps drawing on the host
     base_sampler, base_seed, _base_draw = "host", 0, 0
@@ -175,14 +188,7 @@ class CaSPR(nn.Module):
         if cnf_steps == "frame":
             if cnf_method != "rk4":
                 raise ValueError("cnf_steps=\"frame\" chooses RK4 step counts: it does not combine with cnf_method=%r" % (cnf_method,))
-            if not (isinstance(cnf_steps_max, int) and 2 <= cnf_steps_max <= 256 and cnf_steps_max & (cnf_steps_max - 1) == 0):
-                raise ValueError("cnf_steps_max must be a power of two in 2..256, got %r" % (cnf_steps_max,))
-            if not (1.0 <= float(cnf_steps_safety) < float("inf")):
-                raise ValueError("cnf_steps_safety must be finite and >= 1, got %r" % (cnf_steps_safety,))
-            if int(cnf_steps_points) < 1:
-                raise ValueError("cnf_steps_points must be positive, got %r" % (cnf_steps_points,))
-            if cnf_steps_tol is not None and not (0.0 < float(cnf_steps_tol) < float("inf")):
-                raise ValueError("cnf_steps_tol must be positive and finite, got %r" % (cnf_steps_tol,))
+            _check_pilot_options(cnf_steps_max, cnf_steps_safety, cnf_steps_points, cnf_steps_tol)
         self.cnf_steps = cnf_steps
         self.cnf_steps_tol = cnf_steps_tol
         self.cnf_steps_safety = float(cnf_steps_safety)
@@ -434,29 +440,16 @@ class CaSPR(nn.Module):
         blocks = [l for l in self.point_cnf.chain if isinstance(l, CNF)]
         if any(b.method != "rk4" for b in blocks):
             raise ValueError("cnf_steps=\"frame\" chooses RK4 step counts: a dopri5 block has none")
-        BT, n = y.shape[0], y.shape[1]
-        g, s_max = min(self.cnf_steps_points, n), int(self.cnf_steps_max)
+        g, s_max = min(self.cnf_steps_points, y.shape[1]), int(self.cnf_steps_max)
         tol = self.cnf_steps_tol if self.cnf_steps_tol is not None else (self.check_tol if self.check_tol is not None else 1e-5)
         yp = y[:, :g].contiguous()
-
-        def run_rung(tab):
-            for b in blocks:
-                b.frame_steps, b.frame_order, b.frame_max_steps = tab, None, s_max
-            return self.point_cnf(yp, z, reverse=True)
         try:
             for b in blocks:
                 b._hyper = b.hyper_of(z)
             if ops.BEFORE_CNF_LAUNCH is not None:          # reconstruct()'s deferred T-NOCS regression: in front of the pilot, not of the solve
                 hook, ops.BEFORE_CNF_LAUNCH = ops.BEFORE_CNF_LAUNCH, None
                 hook()
-            for b in blocks:
-                b._count_evals, b.odefunc._count_evals, b._narrow = False, False, True
-            try:
-                with ops.timed("cnf_pilot"):
-                    steps, order, info = ops.cnf_frame_steps(run_rung, BT, g, tol, self.cnf_steps_safety, s_max, device=y.device)
-            finally:
-                for b in blocks:
-                    b._count_evals, b.odefunc._count_evals, b._narrow = True, True, False
+            steps, order, info = self._pilot_frame_steps(blocks, yp, z, tol, s_max)
             for b in blocks:
                 b.frame_steps, b.frame_order, b.frame_max_steps = steps, order, s_max
             with ops.timed("cnf_main"):
@@ -472,6 +465,42 @@ class CaSPR(nn.Module):
         if self.check_tol is not None and not torch.cuda.is_current_stream_capturing():
             self._guard_cnf_frames(blocks, y, z, x, steps, s_max)
         return x
+
+    def _pilot_frame_steps(self, blocks, yp, z, tol, s_max):
+        """The pilot ladder of ops.cnf_frame_steps on the pilot points yp (BT,g,3) through the whole flow: narrow kernel, one table for all
+        blocks, not counted by get_nfe() (the callers add info["pilot_steps"]).  Expects every block's `_hyper` in place and leaves the
+        last rung's table on the blocks: the caller sets or clears `frame_steps`.  -> (steps, order, info)."""
+        def run_rung(tab):
+            for b in blocks:
+                b.frame_steps, b.frame_order, b.frame_max_steps = tab, None, s_max
+            return self.point_cnf(yp, z, reverse=True)
+        for b in blocks:
+            b._count_evals, b.odefunc._count_evals, b._narrow = False, False, True
+        try:
+            with ops.timed("cnf_pilot"):
+                return ops.cnf_frame_steps(run_rung, yp.shape[0], yp.shape[1], tol, self.cnf_steps_safety, s_max, device=yp.device)
+        finally:
+            for b in blocks:
+                b._count_evals, b.odefunc._count_evals, b._narrow = True, True, False
+
+    def _pilot_for_gradient(self, y, z):
+        """decode(differentiable=True, frame_steps="pilot"): the step counts the inference route would choose for (y, z) -- the same pilot
+        on the same first cnf_steps_points samples with the model's cnf_steps_tol / _safety / _max, under no_grad on detached tensors
+        (the counts are held fixed by the gradient).  A capped frame reports through the deferred channel.  -> (steps, order, info)."""
+        from .cnf import CNF
+        _check_pilot_options(self.cnf_steps_max, self.cnf_steps_safety, self.cnf_steps_points, self.cnf_steps_tol)
+        blocks = [l for l in self.point_cnf.chain if isinstance(l, CNF)]
+        g, s_max = min(self.cnf_steps_points, y.shape[1]), int(self.cnf_steps_max)
+        tol = self.cnf_steps_tol if self.cnf_steps_tol is not None else (self.check_tol if self.check_tol is not None else 1e-5)
+        with torch.no_grad():
+            yd, zd = y.detach(), z.detach()
+            try:
+                for b in blocks:
+                    b._hyper = b.hyper_of(zd)
+                return self._pilot_frame_steps(blocks, yd[:, :g].contiguous(), zd, tol, s_max)
+            finally:
+                for b in blocks:
+                    b.frame_steps, b.frame_order, b.frame_max_steps, b._hyper = None, None, None, None
 
     def _guard_cnf_frames(self, blocks, y, z, x, steps, s_max):
         """The accuracy guard of a frame-mode solve: the first check_points samples of every frame once more with the table S_f // 2 on
@@ -609,21 +638,25 @@ class CaSPR(nn.Module):
             y = y.view((B, 1, num_points, input_dim)).expand((B, T, num_points, input_dim)).reshape((B * T, num_points, input_dim))
         return y.contiguous(), logp_y
 
-    def _check_differentiable(self, what):
+    def _check_differentiable(self, what, frame_steps=None):
         """decode(differentiable=True) / reconstruct(differentiable=True): the options the gradient route does not cover, refused with
-        the reason (train/flow_grad.py: point_cnf_sample_train states the rest -- GPU tensors, the 512-wide ODE function, ops.CNF_BF16X6)."""
+        the reason (train/flow_grad.py: point_cnf_sample_train states the rest -- GPU tensors, the 512-wide ODE function, ops.CNF_BF16X6).
+        With frame_steps (a table or "pilot") the per-frame counts are the caller's choice and cnf_steps="frame" is no obstacle."""
         from .cnf import CNF
         if not torch.is_grad_enabled():
             raise ValueError("%s(differentiable=True) records a gradient, but grad mode is off (torch.no_grad()): drop the keyword for inference" % what)
-        if self.cnf_steps == "frame":
+        if frame_steps is None and self.cnf_steps == "frame":
             raise ValueError("%s(differentiable=True) differentiates the uniform RK4 solve: no gradient through per-frame step counts "
-                             "(cnf_steps=\"frame\" is an inference option)" % what)
+                             "chosen inside the call (cnf_steps=\"frame\" is an inference option); pass frame_steps=\"pilot\" or a table "
+                             "of counts to differentiate the solve with every frame's count held fixed" % what)
+        if frame_steps is not None and not torch.is_tensor(frame_steps) and frame_steps != "pilot":
+            raise ValueError("%s: frame_steps must be None, \"pilot\" or a (B*T,) int32 tensor of RK4 step counts, got %r" % (what, frame_steps))
         if any(isinstance(l, CNF) and l.method != "rk4" for l in self.point_cnf.chain):
             raise ValueError("%s(differentiable=True) differentiates the RK4 solve: no gradient through the adaptive solve "
                              "(cnf_method=\"dopri5\" is an inference option)" % what)
 
     def decode(self, z, num_points=1024, constant_in_time=False, truncate_std=None, sample_contours=None, y=None, _early=None, frame_ids=None,
-               differentiable=False):
+               frame_steps=None, differentiable=False):
         """caspr.py:204-267.  `y` (B,T,num_points,3) optionally supplies the base samples.
         frame_ids (device sampler only; ignored with the host sampler or a given `y`): the global ids the draw is keyed by, int64,
         B*T of them (sequence * T + t) or, with constant_in_time, B (see _base_frame_ids); default: this batch is sequences 0 .. B-1.
@@ -632,9 +665,17 @@ class CaSPR(nn.Module):
         parameter of the point CNF, as the reference's decode is (caspr.py:262 through torchdiffeq): the sampling solve runs as one
         autograd node per block with a tape of (BT,n,3) tensors (train/flow_grad.py: point_cnf_sample_train; discretise-then-optimise:
         the gradient of the RK4 map itself).  Needs grad mode, GPU tensors, uniform RK4 steps (not cnf_method="dopri5", not
-        cnf_steps="frame"): otherwise a ValueError says which; no guard on this route."""
+        cnf_steps="frame"): otherwise a ValueError says which; no guard on this route.
+        frame_steps (with differentiable=True only; inference has cnf_steps="frame"): None (default) = cnf_rk4_steps for every frame.  A
+        (B*T,) int32 tensor on z's device = the RK4 step count of every frame, 1..cnf_steps_max; "pilot" = chosen here as the inference
+        route chooses them (the pilot of cnf_steps="frame" with the model's cnf_steps_tol / _safety / _max / _points, run under no_grad;
+        get_nfe() counts pilot + solve; last_frame_steps = (steps, order, info) afterwards).  The gradient is that of the RK4 map with
+        every frame's count held fixed (train/flow_grad.py: CnfSampleSolveFrames); every CNF block takes the same table.  Works on a
+        model built with either cnf_steps."""
+        if frame_steps is not None and not differentiable:
+            raise ValueError("decode: frame_steps comes with differentiable=True (inference chooses per-frame counts with cnf_steps=\"frame\")")
         if differentiable:
-            self._check_differentiable("decode")
+            self._check_differentiable("decode", frame_steps)
         B, T, H = z.size()
         input_dim = self.cnf_args.input_dim
         given = y is not None
@@ -649,7 +690,10 @@ class CaSPR(nn.Module):
         z = z.reshape((B * T, H))
         if differentiable:
             from ..train.flow_grad import point_cnf_sample_train
-            x = point_cnf_sample_train(self.point_cnf, y, z)
+            if frame_steps is None:
+                x = point_cnf_sample_train(self.point_cnf, y, z)
+            else:
+                x = self._decode_differentiable_frames(y, z, frame_steps)
         elif self.cnf_steps == "frame" and y.is_cuda:
             x = self._decode_frame_steps(y, z)
         else:
@@ -658,6 +702,27 @@ class CaSPR(nn.Module):
             if guard is not None:
                 self._guard_cnf_end(guard, x)
         return y.view((B, T, num_points, input_dim)), logp_y.view((B, T, num_points)), x.view((B, T, num_points, input_dim))
+
+    def _decode_differentiable_frames(self, y, z, frame_steps):
+        """decode(differentiable=True)'s solve with a step count per frame: the table as given, or the pilot's.  y (BT,n,3), z (BT,H)."""
+        from .cnf import CNF
+        from ..train.flow_grad import point_cnf_sample_train
+        if not (y.is_cuda and z.is_cuda):
+            raise ValueError("decode(differentiable=True) runs on the GPU only (HIP kernels): z and y must be GPU tensors")
+        order = info = None
+        if torch.is_tensor(frame_steps):
+            steps = frame_steps
+        else:
+            steps, order, info = self._pilot_for_gradient(y, z)
+        x = point_cnf_sample_train(self.point_cnf, y, z, steps, int(self.cnf_steps_max))
+        if info is not None:
+            pilot_evals = 4 * info["pilot_steps"].max()
+            for b in self.point_cnf.chain:
+                if isinstance(b, CNF):
+                    b.last_pilot_steps_per_frame = info["pilot_steps"]
+                    b.odefunc._num_evals += pilot_evals.to(b.odefunc._num_evals.dtype)   # on the device, as the inference route counts
+        self.last_frame_steps = (steps, order, info)
+        return x
 
     @staticmethod
     def _sequence_frame_ids(sequence_ids, B, T, constant_in_time, device):
@@ -670,11 +735,13 @@ class CaSPR(nn.Module):
         return (seq.view(B, 1) * T + torch.arange(T, device=device, dtype=torch.int64).view(1, T)).reshape(-1)
 
     def reconstruct(self, x, num_points=1024, constant_in_time=False, timestamps=None, max_timestamp=5.0,
-                    truncate_std=None, sample_contours=None, y=None, check_tol=_UNSET, sequence_ids=None, differentiable=False):
+                    truncate_std=None, sample_contours=None, y=None, check_tol=_UNSET, sequence_ids=None, frame_steps=None,
+                    differentiable=False):
         """caspr.py:269-308 -> (y, logp_y, x, tnocs_pred).  `y` (B,T,num_points,3) optionally supplies the base samples.
         differentiable=True: the plain serial composition the reference has -- encode -> aggregate_and_solve_latent ->
         decode(differentiable=True) -- on the current stream, recorded by autograd (encoder, latent ODE and point CNF each through their
         training route); no side streams, no early latent solve, no accuracy guard.  Same return tuple; see decode() for what it needs.
+        frame_steps (with differentiable=True only): None, a (B*T,) int32 table of RK4 step counts or "pilot", handed to decode().
         check_tol: the accuracy guard's tolerance for THIS call (default: the model's `check_tol` attribute; None = off).
         sequence_ids (device sampler only; ignored with the host sampler or a given `y`): int64 (B,), the global index of each
         sequence (default arange(B)); a shard that passes its sequences' global indices draws what the unsharded batch draws.
@@ -683,11 +750,13 @@ class CaSPR(nn.Module):
             prev, self.check_tol = self.check_tol, check_tol
             try:
                 return self.reconstruct(x, num_points, constant_in_time, timestamps, max_timestamp, truncate_std, sample_contours, y,
-                                        sequence_ids=sequence_ids, differentiable=differentiable)
+                                        sequence_ids=sequence_ids, frame_steps=frame_steps, differentiable=differentiable)
             finally:
                 self.check_tol = prev
+        if frame_steps is not None and not differentiable:
+            raise ValueError("reconstruct: frame_steps comes with differentiable=True (inference chooses per-frame counts with cnf_steps=\"frame\")")
         if differentiable:
-            self._check_differentiable("reconstruct")
+            self._check_differentiable("reconstruct", frame_steps)
             B, T, N, _ = x.size()
             all_times = x[:, :, 0, 3] / max_timestamp if timestamps is None else timestamps.view((1, -1)).repeat((B, 1)).to(x)
             z0, tnocs_pred = self.encode(x)
@@ -695,7 +764,8 @@ class CaSPR(nn.Module):
             if self.base_sampler == "device" and y is None and sequence_ids is not None:
                 frame_ids = self._sequence_frame_ids(sequence_ids, B, T, constant_in_time, x.device)
             z = self.aggregate_and_solve_latent(z0, all_times)
-            y, logp_y, x = self.decode(z, num_points, constant_in_time, truncate_std, sample_contours, y=y, frame_ids=frame_ids, differentiable=True)
+            y, logp_y, x = self.decode(z, num_points, constant_in_time, truncate_std, sample_contours, y=y, frame_ids=frame_ids, frame_steps=frame_steps,
+                                       differentiable=True)
             return y, logp_y, x, tnocs_pred
         with torch.no_grad():
             B, T, N, _ = x.size()

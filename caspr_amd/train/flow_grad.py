@@ -16,7 +16,8 @@ activation into the GEMM epilogue and recomputing instead of storing the layer p
 (DESIGN.md section 7).  No CPU path: everything below requires GPU tensors.
 
 The SAMPLING direction of the point CNF (decode(differentiable=True); cnf.py:70-128 with reverse = True, caspr.py:262) is at the end of the
-file: CnfSampleSolve / point_cnf_sample_train, one node per block on value rows only.
+file: CnfSampleSolve / point_cnf_sample_train, one node per block on value rows only; CnfSampleSolveFrames is the same node with an RK4
+step count per frame (decode(differentiable=True, frame_steps=...)).
 """
 import weakref
 
@@ -985,9 +986,140 @@ class CnfSampleSolve(torch.autograd.Function):
         return (gy, d_hyp[0], d_hyp[1], d_hyp[2], d_hyp[3], dt_end, None, None, None, None) + tuple(d_wb)
 
 
-def cnf_block_sample_train(block, y, context):
+def _frames_plan(steps, max_steps):
+    """What CnfSampleSolveFrames needs of its step table on the host: ONE read of (table, launch order) -> counts per frame, the
+    launch order as a list, and the order tensor itself.  An entry outside 1..max_steps is refused with the frame's index: the
+    kernel's clamp is for memory safety, not an interface."""
+    if not torch.is_tensor(steps) or steps.dim() != 1 or steps.dtype != torch.int32:
+        raise ValueError("frame_steps must be a (BT,) int32 tensor of RK4 step counts, got %s" %
+                         ("%s %s" % (steps.dtype, tuple(steps.shape)) if torch.is_tensor(steps) else type(steps).__name__))
+    order = ops.cnf_steps_order(steps)                                   # longest first, stable
+    host = torch.stack([steps, order]).cpu()                             # the one synchronisation of the solve
+    counts, perm = host[0].tolist(), host[1].tolist()
+    for f, s in enumerate(counts):
+        if not 1 <= s <= int(max_steps):
+            raise ValueError("frame_steps: frame %d asks for %d RK4 steps, outside 1..%d" % (f, s, int(max_steps)))
+    pos = [counts[f] for f in perm]
+    if sorted(perm) != list(range(len(counts))) or any(a < b for a, b in zip(pos, pos[1:])):
+        raise RuntimeError("frame_steps: the launch order is not the longest-first permutation of the frames")
+    return counts, perm, order
+
+
+class CnfSampleSolveFrames(torch.autograd.Function):
+    """CnfSampleSolve with an RK4 step count PER FRAME, each held fixed: the gradient of the map frame f -> RK4 with S_f steps of
+    h_f = -t_end / S_f (the count is piecewise constant in the parameters, so this is the gradient wherever it is defined; the EMD
+    gradients hold their matching fixed in the same way).  Forward = one launch of caspr_cnf_sample_tape_frames_f32 in the order longest
+    first (ops.cnf_steps_order), which writes frame order[p]'s tape at POSITION p, steps s < S_f only; the tape has max_f S_f step rows
+    and the rows a frame did not write are never read.  The forward reads the table to the host ONCE (steps.cpu()): this route is a
+    Python reverse sweep and was never capturable, so one synchronisation per solve is its price for knowing the loop bounds.
+    Backward = the sweep of CnfSampleSolve with (1) the step size and the stage times per frame -- h_f, t_f = t_end + (s + c_i) h_f, the
+    time handed to the evaluation as a layer-major vector built from an (F,) leaf, so that dL/dt_f comes back per frame; (2) at step s
+    only the first F_s = #{f : S_f > s} positions taking part: the tape, the cotangent and the hyper rows (permuted to launch order once)
+    are sliced, the value kernels run on F_s n rows, finished frames cost nothing; (3) dL/dt_end = sum_f (dt0_f - dh_f / S_f), both
+    accumulated per frame in f64.  dL/dy and the hyper gradients go back to frame order by index assignment over unique indices: no
+    atomics, two runs give the same bits.
+    y (BT,n,3), G_lm / Bb_lm / tg_lm / tb_lm layer-major, t_end 0-dim tensor, w1x / w2x, steps (BT,) int32 on y's device, max_steps (the
+    largest count a frame may ask for), widths, then w0, b0, ..., w3, b3 -> x (BT,n,3)."""
+
+    @staticmethod
+    def forward(ctx, y, G_lm, Bb_lm, tg_lm, tb_lm, t_end, w1x, w2x, steps, max_steps, widths, *wb):
+        BT, n, _ = y.shape
+        if steps.shape[0] != BT:
+            raise ValueError("frame_steps holds %d counts for %d frames" % (steps.shape[0], BT))
+        counts, perm, order = _frames_plan(steps, max_steps)
+        hyper, tcol = _hyper_for_kernel(G_lm, Bb_lm, tg_lm, tb_lm, BT, widths)
+        w0, b0, w1, b1, w2, b2, w3, b3 = [t_.detach().contiguous() for t_ in wb]
+        x, ys, ka = T.cnf_sample_tape_frames(y.detach().contiguous(), hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3,
+                                             t_end.detach().reshape(1).contiguous(), steps, max(counts), order)
+        ctx.save_for_backward(ys, ka, G_lm, Bb_lm, tg_lm, tb_lm, t_end, order)
+        ctx.counts, ctx.perm, ctx.widths, ctx.wb = counts, perm, widths, wb
+        return x
+
+    @staticmethod
+    def backward(ctx, gy):
+        ys, ka, G_lm, Bb_lm, tg_lm, tb_lm, t_end, order = ctx.saved_tensors
+        widths, wb = ctx.widths, ctx.wb
+        S_alloc, _, BT, n, _ = ys.shape
+        dev = ys.device
+        pidx = order.long()                                            # position p of the launch order holds frame pidx[p]
+        S_pos = [ctx.counts[f] for f in ctx.perm]                      # non-increasing
+        t0 = t_end.detach().reshape(())
+        S_t = torch.tensor(S_pos, device=dev, dtype=t0.dtype)
+        h_all = -t0 / S_t                                              # (BT,) launch order: h_f = -t_end / S_f
+        gy = gy.contiguous()[pidx]                                     # launch order from here on
+        in_launch_order = lambda v: torch.cat([u[pidx].reshape(-1) for u in _layer_views(v.detach(), BT, widths)])
+        hyp_all = [_layer_views(in_launch_order(v), BT, widths) for v in (G_lm, Bb_lm, tg_lm, tb_lm)]
+        d_hyp = [torch.zeros_like(v) for v in (G_lm, Bb_lm, tg_lm, tb_lm)]            # launch order, layer-major over all BT frames
+        wsel = [i for i, w in enumerate(wb) if w.requires_grad]
+        d_wb = [torch.zeros_like(w) if w.requires_grad else None for w in wb]
+        dh = torch.zeros(BT, device=dev, dtype=torch.float64)          # dL/dh_f and dL/d(start time) per frame, summed in f64
+        dt0 = torch.zeros(BT, device=dev, dtype=torch.float64)
+        dots = lambda u, v: (u.double() * v.double()).flatten(1).sum(1)
+        CW = (1.0 / 6.0, 2.0 / 6.0, 2.0 / 6.0, 1.0 / 6.0)
+        TC = (0.0, 0.5, 0.5, 1.0)
+        F_cur, hyp, acc = 0, None, None
+
+        def flush():                                                   # the prefix's hyper gradients into the rows of that prefix
+            if acc is not None:
+                for buf, part in zip(d_hyp, acc):
+                    for full, pre in zip(_layer_views(buf, BT, widths), _layer_views(part, F_cur, widths)):
+                        full[:F_cur].add_(pre)
+        for s in range(S_alloc - 1, -1, -1):
+            Fs = sum(1 for c in S_pos if c > s)                        # the frames still integrating at step s: a prefix
+            if Fs != F_cur:                                            # (grows as s falls: once per distinct count)
+                flush()
+                F_cur = Fs
+                hyp = [torch.cat([u[:Fs].reshape(-1) for u in views]).requires_grad_(True) for views in hyp_all]
+                acc = [torch.zeros_like(v) for v in hyp]
+            h = h_all[:Fs].view(Fs, 1, 1)
+            g_s = gy[:Fs]
+            k = ka[s]
+            dh[:Fs] += dots(g_s, k[0, :Fs] + 2.0 * k[1, :Fs] + 2.0 * k[2, :Fs] + k[3, :Fs]) / 6.0
+            gy_next, g_in = g_s.clone(), None                          # g_in: cotangent of the NEXT stage's input
+            for st in (3, 2, 1, 0):
+                ka_bar = (CW[st] * h) * g_s
+                if g_in is not None:
+                    ka_bar = torch.addcmul(ka_bar, g_in, TC[st + 1] * h)
+                with torch.enable_grad():
+                    tF = (t0 + (s + TC[st]) * h_all[:Fs]).detach().requires_grad_(True)
+                    t = torch.cat([tF.unsqueeze(1).expand(Fs, w).reshape(-1) for w in widths])      # layer-major, as G_lm + t * tg_lm wants it
+                    y_in = ys[s, st, :Fs].detach().requires_grad_(True)
+                    a = _cnf_eval_value(wb, t, y_in, hyp[0], hyp[1], hyp[2], hyp[3], Fs, n, widths)
+                    g = torch.autograd.grad(a, [y_in, tF] + hyp + [wb[i] for i in wsel], ka_bar)
+                del a
+                g_in = g[0]
+                for buf, gi in zip(acc, g[2:6]):
+                    buf.add_(gi)
+                for i, gi in zip(wsel, g[6:]):
+                    d_wb[i].add_(gi)
+                dt0[:Fs] += g[1].double()                              # through the stage time t_f = t_end + (s + TC) h_f
+                dh[:Fs] += g[1].double() * (s + TC[st])
+                if st > 0:
+                    dh[:Fs] += TC[st] * dots(g_in, k[st - 1, :Fs])     # through the stage input y + TC h_f k_{st-1}
+                gy_next.add_(g_in)
+                del g
+            gy[:Fs] = gy_next
+        flush()
+        dt_end = (dt0 - dh / S_t.double()).sum().to(t_end.dtype).reshape(t_end.shape)      # h_f = -t_end / S_f
+        # back to frame order: an index assignment over the permutation (unique indices)
+        dy = torch.empty_like(gy)
+        dy[pidx] = gy
+        outs = []
+        for buf in d_hyp:
+            o = torch.empty_like(buf)
+            for dst, src in zip(_layer_views(o, BT, widths), _layer_views(buf, BT, widths)):
+                dst[pidx] = src
+            outs.append(o)
+        return (dy, outs[0], outs[1], outs[2], outs[3], dt_end, None, None, None, None, None) + tuple(d_wb)
+
+
+def cnf_block_sample_train(block, y, context, frame_steps=None, max_steps=None):
     """One CNF block in the sampling direction, differentiable in y, the context and every parameter of the block: y (BT,n,3),
-    context (BT,zdim) -> x (BT,n,3) at t = 0 after `block.rk4_steps` RK4 steps from sqrt_end_time^2."""
+    context (BT,zdim) -> x (BT,n,3) at t = 0 after `block.rk4_steps` RK4 steps from sqrt_end_time^2.
+    frame_steps: a (BT,) int32 tensor on y's device gives every frame its own step count, 1..max_steps (default: the kernel's limit,
+    ops.CNF_MAX_TABLE_STEPS), held fixed under differentiation (CnfSampleSolveFrames); `block.rk4_steps` is not used then."""
+    if frame_steps is not None:
+        return _cnf_block_sample_train_frames(block, y, context, frame_steps, ops.CNF_MAX_TABLE_STEPS if max_steps is None else int(max_steps))
     layers = block.odefunc.diffeq.layers
     widths = tuple(l._layer.weight.shape[0] for l in layers)
     if widths != (512, 512, 512, 3) or block.method != "rk4" or block.frame_steps is not None:
@@ -1002,10 +1134,29 @@ def cnf_block_sample_train(block, y, context):
     return x
 
 
-def point_cnf_sample_train(flow, y, context):
+def _cnf_block_sample_train_frames(block, y, context, frame_steps, max_steps):
+    """cnf_block_sample_train with a step table: the same block through CnfSampleSolveFrames; _num_evals = 4 max_f S_f (on the device)."""
+    layers = block.odefunc.diffeq.layers
+    widths = tuple(l._layer.weight.shape[0] for l in layers)
+    if widths != (512, 512, 512, 3) or block.method != "rk4":
+        raise ValueError("the differentiable sampling solve is built for the 3-512-512-512-3 ODE function on RK4 steps "
+                         "(got widths %s, method %r)" % (widths, block.method))
+    ops._chk_frame_table("frame_steps", frame_steps, y.shape[0], y.device)
+    G_lm, Bb_lm, tg_lm, tb_lm, widths = _hyper_layer_major(block, context)
+    t_end = block.sqrt_end_time * block.sqrt_end_time if block.train_T else torch.tensor(float(block.T), device=y.device)
+    w1x, w2x = block._weights_x6()
+    wb = [p_ for l in layers for p_ in (l._layer.weight, l._layer.bias)]
+    x = CnfSampleSolveFrames.apply(y, G_lm, Bb_lm, tg_lm, tb_lm, t_end, w1x, w2x, frame_steps, max_steps, widths, *wb)
+    block.odefunc._num_evals.copy_(4 * frame_steps.max())
+    return x
+
+
+def point_cnf_sample_train(flow, y, context, frame_steps=None, max_steps=None):
     """SequentialFlow in the reverse (sampling) direction (cnf.py:33-48 with reverse = True, logpx = None), differentiable: the chain
     walked backwards, MovingBatchNorm1d(reverse=True) in torch, every CNF block through CnfSampleSolve.  y (BT,n,3), context (BT,zdim)
-    -> x (BT,n,3).  No fallback: what the route needs is stated in the error."""
+    -> x (BT,n,3).  No fallback: what the route needs is stated in the error.
+    frame_steps (BT,) int32 on y's device: every CNF block of the chain takes this table of step counts (CnfSampleSolveFrames), as the
+    inference route shares one table; max_steps: the largest count an entry may hold (see cnf_block_sample_train)."""
     from ..models.cnf import CNF
     if not (torch.is_tensor(y) and torch.is_tensor(context) and y.is_cuda and context.is_cuda):
         raise ValueError("point_cnf_sample_train runs on the GPU only (HIP kernels): y and context must be GPU tensors")
@@ -1016,7 +1167,7 @@ def point_cnf_sample_train(flow, y, context):
     x = y.reshape(-1, y.shape[-2], y.shape[-1]).float()
     for layer in reversed(flow.chain):
         if isinstance(layer, CNF):
-            x = cnf_block_sample_train(layer, x, context)
+            x = cnf_block_sample_train(layer, x, context, frame_steps, max_steps)
         else:
             x = layer(x, context, None, None, True)
     return x

@@ -224,6 +224,46 @@ def cnf_sample_tape(y, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_end, ste
     return out, ys, ka
 
 
+def cnf_sample_tape_frames(y, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_end, steps, max_steps, order=None, ys=None, ka=None):
+    """cnf_sample_tape with an RK4 step count per frame (caspr_cnf_sample_tape_frames_f32; the same kernel).  steps (BT,) int32 GPU
+    tensor: frame f takes S_f = min(max(steps[f], 0), max_steps) steps of h_f = -t_end / S_f (0 skips the frame: its rows of x_0 stay
+    as allocated); order (BT,) int32 GPU tensor or None: the launch order (ops.cnf_steps_order).  The tape is written in LAUNCH order:
+    position p of the frame axis holds frame order[p] (p itself without an order), rows s < S_f only -- the rest of ys / ka is left
+    as it was.  ys / ka (max_steps,4,BT,n,3) may be handed in (a test poisons them); allocated with torch.empty otherwise.
+    -> x_0 (BT,n,3), ys, ka."""
+    _chk_f32(y, hyper, tcol, w0, b0, b1, b2, w3, b3, t_end, ys, ka)
+    if y.dim() != 3 or y.shape[2] != 3:
+        raise ValueError("cnf_sample_tape_frames: y must be (BT,n,3), got %s" % (tuple(y.shape),))
+    BT, n, _ = y.shape
+    if hyper.dim() != 2 or hyper.shape[0] != BT or hyper.stride(1) != 1 or hyper.shape[1] < 2 * (3 * 512 + 3) or tcol.numel() < 2 * (3 * 512 + 3):
+        raise ValueError("cnf_sample_tape_frames: hyper must be (BT, >= 3078) rows and tcol hold 3078 floats, got %s / %s" % (tuple(hyper.shape), tuple(tcol.shape)))
+    if tuple(w0.shape) != (512, 3) or tuple(w3.shape) != (3, 512) or b0.numel() != 512 or b1.numel() != 512 or b2.numel() != 512 or b3.numel() != 3:
+        raise ValueError("cnf_sample_tape_frames: the kernel is built for the 3-512-512-512-3 ODE function")
+    if w1x is None or w2x is None or w1x.numel() != _lib.load().caspr_cnf_x6_packed_bytes() or w2x.numel() != w1x.numel():
+        raise ValueError("cnf_sample_tape_frames: the bf16x6 weight packs w1x / w2x (ops.pack_cnf_x6) are required")
+    if t_end.numel() != 1 or not t_end.is_cuda:
+        raise ValueError("cnf_sample_tape_frames: t_end must be a one-element device tensor")
+    ops._chk_frame_table("steps", steps, BT, y.device)
+    if order is not None:
+        ops._chk_frame_table("order", order, BT, y.device)
+    max_steps = int(max_steps)
+    if not 1 <= max_steps <= ops.CNF_MAX_TABLE_STEPS:
+        raise ValueError("cnf_sample_tape_frames: max_steps must lie in 1..%d, got %d" % (ops.CNF_MAX_TABLE_STEPS, max_steps))
+    dev = y.device
+    shape = (max_steps, 4, BT, n, 3)           # max_steps is the kernel's clamp AND the tape's step rows: they must be the same number
+    for name, t in (("ys", ys), ("ka", ka)):
+        if t is not None and (tuple(t.shape) != shape or t.device != dev or not t.is_contiguous()):
+            raise ValueError("cnf_sample_tape_frames: %s must be a contiguous %s tensor on %s, got %s on %s" % (name, shape, dev, tuple(t.shape), t.device))
+    out = torch.empty(BT, n, 3, device=dev, dtype=torch.float32)
+    ys = torch.empty(shape, device=dev, dtype=torch.float32) if ys is None else ys
+    ka = torch.empty(shape, device=dev, dtype=torch.float32) if ka is None else ka
+    with ops.timed("cnf_sample_tape"):
+        _lib.check(_lib.load().caspr_cnf_sample_tape_frames_f32(_p(y), _p(hyper), hyper.stride(0), _p(tcol), _p(w0), _p(b0), _p(w1x), _p(b1), _p(w2x), _p(b2),
+                                                                _p(w3), _p(b3), 512, _p(t_end), _p(steps), max_steps, _p(order), _p(out), _p(ys), _p(ka),
+                                                                BT, n, _stream()), "caspr_cnf_sample_tape_frames_f32")
+    return out, ys, ka
+
+
 # ---- the gated softplus layers on value rows only (csrc/backward_flow_value.hip): R = frames * n rows, point p in row p.
 # gate / beta (frames, C) contiguous; the backward wrappers return dgate / dbeta (frames, C) with the point splits already summed.
 # The (rows, C) tensors may hold MORE than R rows: the caller rounds the row count up (to the 128 rows the bf16x6 conv kernels want of

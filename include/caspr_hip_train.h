@@ -245,6 +245,20 @@ int caspr_cnf_sample_tape_f32(const float *y_in, const float *hyper, int ldh, co
                               const void *w1x, const float *b1, const void *w2x, const float *b2, const float *w3, const float *b3,
                               int H, const float *t_end, int steps, float *y_out, float *ys, float *ka, int BT, int n, void *stream);
 
+/* The same solve (cnf.py:70-128 reversed, as caspr.py:262 runs it) with an RK4 step count PER FRAME and its tape in LAUNCH ORDER
+ * (train/flow_grad.py: CnfSampleSolveFrames); the same kernel.  steps_tab (BT) int32, non-NULL: frame f takes S_f =
+ * min(max(steps_tab[f], 0), max_steps) steps of h_f = -t_end / S_f; S_f = 0 skips the frame (nothing of it is read or written).
+ * 1 <= max_steps <= 4096, and max_steps is ALSO the number of step rows the caller allocated in ys / ka: the clamp keeps the stores
+ * inside the tape.  order (BT) int32 or NULL: workgroup row p works on frame order[p] (a row outside 0..BT-1 is skipped); NULL: p.
+ * Frame order[p] reads y_in / hyper and writes y_out at its own row, and writes its tape at POSITION p: ys / ka
+ * (max_steps,4,BT,n,3)[s][stage][p] for s < S_f only; rows s >= S_f of position p are not written.  With order = longest first the
+ * frames active at step s are a prefix of the tape's frame axis.  Everything else as caspr_cnf_sample_tape_f32 requires; a table of
+ * all S without an order gives its bits.                                                                                            */
+int caspr_cnf_sample_tape_frames_f32(const float *y_in, const float *hyper, int ldh, const float *tcol, const float *w0, const float *b0,
+                                     const void *w1x, const float *b1, const void *w2x, const float *b2, const float *w3, const float *b3,
+                                     int H, const float *t_end, const int32_t *steps_tab, int max_steps, const int32_t *order, float *y_out,
+                                     float *ys, float *ka, int BT, int n, void *stream);
+
 /* The gated softplus layers of the ODE function on VALUE rows only (csrc/backward_flow_value.hip), for the reverse sweep of the
  * sampling solve above (cnf.py:70-128 with logpx = None, caspr.py:262: no Hutchinson tangent, no log-density): R = frames n rows,
  * point p in row p, frame f = p / n; C % 4 == 0; b, gate, beta, Z, H, dH, dZ 16-byte aligned with row strides that are multiples
