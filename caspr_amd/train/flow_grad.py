@@ -18,7 +18,12 @@ activation into the GEMM epilogue and recomputing instead of storing the layer p
 The SAMPLING direction of the point CNF (decode(differentiable=True); cnf.py:70-128 with reverse = True, caspr.py:262) is at the end of the
 file: CnfSampleSolve / point_cnf_sample_train, one node per block on value rows only; CnfSampleSolveFrames is the same node with an RK4
 step count per frame (decode(differentiable=True, frame_steps=...)).
+
+The three block nodes -- CnfBlockSolve (forward direction, value + divergence), CnfSampleSolve, CnfSampleSolveFrames -- each launch one
+taping solve kernel forward and share ONE hand-written reverse sweep, _rk4_reverse_sweep, whose docstring states the RK4 algebra; a
+node's backward only describes its variant (outputs, time axis, scalar or per frame) and forms dL/dt_end from what the sweep returns.
 """
+import functools
 import weakref
 
 import torch
@@ -680,14 +685,117 @@ def _hyper_for_kernel(G_lm, Bb_lm, tg_lm, tb_lm, BT, widths):
     return hyper, tcol
 
 
+def _block_node_inputs(block, context, device):
+    """What a block node (CnfBlockSolve, CnfSampleSolve, CnfSampleSolveFrames) takes of its block:
+    -> (G_lm, Bb_lm, tg_lm, tb_lm, widths) of _hyper_layer_major, t_end (0-dim, differentiable when the block trains it), the two packed
+    512 x 512 weights of the solve kernel (w1x, w2x), and [w0, b0, ..., w3, b3]."""
+    hyper = _hyper_layer_major(block, context)
+    t_end = block.sqrt_end_time * block.sqrt_end_time if block.train_T else torch.tensor(float(block.T), device=device)
+    w1x, w2x = block._weights_x6()
+    return hyper, t_end, w1x, w2x, [p_ for l in block.odefunc.diffeq.layers for p_ in (l._layer.weight, l._layer.bias)]
+
+
+def _rk4_reverse_sweep(ys, tapes, gy, g_rest, h_all, stage_time, start_time, evaluate, hyper, wb, widths, prefix=None):
+    """The reverse sweep of a fixed-step RK4 solve of a CNF block, shared by CnfBlockSolve, CnfSampleSolve and CnfSampleSolveFrames.
+
+    The forward kernels integrate, per step s = 0..S-1 with step size h and start time t0,
+        y_i = y + c_i h k_{i-1},   k_i = f(t0 + (s + c_i) h, y_i)   (i = 1..4, c = TC),   y' = y + h sum_i w_i k_i   (w = CW)
+    and tape every y_i (`ys`) and k_i (`tapes[0]`; a second output of f that is only summed, the log-density's integrand, has a tape
+    and a constant cotangent of its own: `tapes[1]`, `g_rest[0]`).  Steps are walked S-1..0 and stages 4..1.
+      Cotangent recursion: with gy = dL/dy', stage i receives  k_i_bar = w_i h gy + c_{i+1} h y_{i+1}_bar  (the second term absent for
+        i = 4), a summed output w_i h times its cotangent.  ONE evaluation is rebuilt from its stored y_i under enable_grad
+        (`evaluate`), the cotangents are pushed through it with torch.autograd.grad, the tape of that evaluation is dropped;
+        y_i_bar comes back and dL/dy = gy + sum_i y_i_bar.
+      h enters by three routes, all summed into dL/dh in f64: the state update (<gy, sum_i w_i k_i>, one dot per output tape), the
+        stage inputs (c_i <y_i_bar, k_{i-1}>) and the stage times ((s + c_i) dL/dt_i).
+      Start time: t_i = t0 + (s + c_i) h also gives dL/dt0 = sum dL/dt_i, kept when `start_time` (t0 = t_end on the reversed axis).
+      Fixed order: stage-major within a step, steps descending, every hyper and weight gradient ADDED into a buffer allocated before
+        the loop -- no atomics, two runs give the same bits.
+
+    What differs between the nodes is handed in:
+      h_all, stage_time(s, c, h) -> the stage time in that node's own rounding (h s + c h forward, t0 + (s + c) h reversed);
+      evaluate(t, y_in, hyp, F) -> the tuple of outputs of one evaluation on F frames (through the module's _cnf_eval_* at call time);
+      prefix None: uniform step count -- h_all 0-dim, a 0-dim time leaf, dots summed over everything, 0-dim f64 accumulators, `hyper`
+        the node's four layer-major tensors made leaves once;
+      prefix = [F_s for s in 0..S-1]: a count per frame, frames in launch order (longest first) -- only the first F_s = #{f: S_f > s}
+        frames take part at step s: h_all (BT,), an (F_s,) time leaf expanded to layer-major, dots and accumulators per frame, the hyper
+        leaves rebuilt from `hyper` (detached, launch order) and the prefix's gradients flushed into the full buffers when F_s changes.
+    -> gy (dL/dy; written in place where a prefix is given), the four hyper gradients, the weight gradients (None where not required),
+    dL/dh and dL/dt0 (None without start_time) in f64."""
+    S, _, BT, _, _ = ys.shape
+    dev = ys.device
+    per_frame = prefix is not None
+    wsel = [i for i, w in enumerate(wb) if w.requires_grad]
+    d_hyp = [torch.zeros_like(v) for v in hyper]
+    d_wb = [torch.zeros_like(w) if w.requires_grad else None for w in wb]
+    dh = torch.zeros((BT,) if per_frame else (), device=dev, dtype=torch.float64)
+    dt0 = torch.zeros((BT,) if per_frame else (), device=dev, dtype=torch.float64) if start_time else None
+    CW = (1.0 / 6.0, 2.0 / 6.0, 2.0 / 6.0, 1.0 / 6.0)              # weights of k1..k4 in the RK4 combination
+    TC = (0.0, 0.5, 0.5, 1.0)                                      # stage i: time + TC[i] h, input y + TC[i] h k_{i-1}
+    if per_frame:
+        dot = lambda u, v: (u.double() * v.double()).flatten(1).sum(1)
+        head = lambda v: v[:F]                                     # the frames taking part, of a tensor whose first axis is the frame
+        F, hyp, acc = 0, None, None
+    else:
+        dot = lambda u, v: (u.double() * v.double()).sum()
+        head = lambda v: v
+        F, hyp, acc = BT, [v.detach().requires_grad_(True) for v in hyper], d_hyp
+
+    def flush():                                                   # the prefix's hyper gradients into the rows of that prefix
+        if acc is not None:
+            for buf, part in zip(d_hyp, acc):
+                for full, pre in zip(_layer_views(buf, BT, widths), _layer_views(part, F, widths)):
+                    full[:F].add_(pre)
+    for s in range(S - 1, -1, -1):
+        if per_frame and prefix[s] != F:                           # (grows as s falls: once per distinct count)
+            flush()
+            F = prefix[s]
+            hyp = [torch.cat([u[:F].reshape(-1) for u in _layer_views(v, BT, widths)]).requires_grad_(True) for v in hyper]
+            acc = [torch.zeros_like(v) for v in hyp]
+        h_F, g_s, dh_s, dt0_s = head(h_all), head(gy), head(dh), head(dt0) if start_time else None
+        h = h_F.view(F, 1, 1) if per_frame else h_F
+        ks = [[head(tp[s, i]) for i in range(4)] for tp in tapes]
+        dh_s += functools.reduce(torch.add, [dot(c, k[0] + 2.0 * k[1] + 2.0 * k[2] + k[3]) for c, k in zip((g_s,) + g_rest, ks)]) / 6.0
+        gy_next, g_in = g_s.clone(), None                          # g_in: cotangent of the NEXT stage's input
+        for st in (3, 2, 1, 0):
+            ka_bar = (CW[st] * h) * g_s
+            if g_in is not None:
+                ka_bar = torch.addcmul(ka_bar, g_in, TC[st + 1] * h)
+            bars = (ka_bar,) + tuple((CW[st] * h) * c for c in g_rest)
+            with torch.enable_grad():
+                tl = stage_time(s, TC[st], h_F).detach().requires_grad_(True)
+                t = torch.cat([tl.unsqueeze(1).expand(F, w).reshape(-1) for w in widths]) if per_frame else tl   # layer-major, as G_lm + t * tg_lm wants it
+                y_in = head(ys[s, st]).detach().requires_grad_(True)
+                outs = evaluate(t, y_in, hyp, F)
+                g = torch.autograd.grad(outs, [y_in, tl] + hyp + [wb[i] for i in wsel], bars)
+            del outs
+            g_in = g[0]
+            for buf, gi in zip(acc, g[2:6]):
+                buf.add_(gi)
+            for i, gi in zip(wsel, g[6:]):
+                d_wb[i].add_(gi)
+            if start_time:
+                dt0_s += g[1].double()                             # through the start time of t = t0 + (s + TC) h
+            dh_s += g[1].double() * (s + TC[st])                   # through the stage time
+            if st > 0:
+                dh_s += TC[st] * dot(g_in, ks[0][st - 1])          # through the stage input y + TC h k_{st-1}
+            gy_next.add_(g_in)
+            del g
+        if per_frame:
+            gy[:F] = gy_next
+        else:
+            gy = gy_next
+    if per_frame:
+        flush()
+    return gy, d_hyp, d_wb, dh, dt0
+
+
 class CnfBlockSolve(torch.autograd.Function):
     """A CNF block's whole RK4 solve (forward direction, Hutchinson divergence for a given e) as ONE autograd node whose tape does not
     grow with the layer width: forward = one launch of caspr_cnf_train_fwd_f32, which keeps every layer product on chip and writes only
-    the (BT,n,3) point state of each evaluation (stage input, stage outputs); backward = a hand-written reverse sweep over steps S-1..0
-    and stages 4..1 that rebuilds ONE evaluation's tape at a time from its stored stage input with the training kernels (SplitLayers ->
-    CnfIn -> CnfHidden -> CnfOut), back-propagates the stage cotangent through it, adds the result to preallocated gradient buffers in
-    a fixed order (stage-major within a step, steps descending: two runs give the same bits) and drops that tape.  The RK4 algebra
-    between the evaluations is done by hand, including dL/dt_end through the step size h = t_end / S and through the stage times.
+    the (BT,n,3) point state of each evaluation (stage input, stage outputs); backward = _rk4_reverse_sweep (see there) with
+    h = t_end / S, stage times h s + c_i h, the evaluation on the training kernels (_cnf_eval_fused: SplitLayers -> CnfIn -> CnfHidden
+    -> CnfOut) with the outputs (a, nd), the log-density's cotangent the same at every step, and dL/dt_end = (dL/dh) / S.
     Discretise-then-optimise, as the taped route: the gradient of the map the forward kernel integrates, up to the rounding between the
     inference-class forward and the training kernels of the recomputation.
     x (BT,n,3), logpx (BT,n,1), G_lm / Bb_lm / tg_lm / tb_lm layer-major as in cnf_block_train, t_end 0-dim tensor, e (BT,n,3),
@@ -710,45 +818,14 @@ class CnfBlockSolve(torch.autograd.Function):
         ys, ka, knd, G_lm, Bb_lm, tg_lm, tb_lm, t_end, e = ctx.saved_tensors
         S, widths, wb = ctx.steps, ctx.widths, ctx.wb
         _, _, BT, n, _ = ys.shape
-        dev = ys.device
-        gy = torch.zeros(BT, n, 3, device=dev, dtype=ys.dtype) if gy is None else gy.contiguous()
-        glp = torch.zeros(BT, n, 1, device=dev, dtype=ys.dtype) if glp is None else glp.contiguous()     # logp_{s+1} = logp_s + ...: the same cotangent at every step
+        gy = torch.zeros(BT, n, 3, device=ys.device, dtype=ys.dtype) if gy is None else gy.contiguous()
+        glp = torch.zeros(BT, n, 1, device=ys.device, dtype=ys.dtype) if glp is None else glp.contiguous()   # logp_{s+1} = logp_s + ...: the same cotangent at every step
         h = (t_end.detach() / S).reshape(())
         e_rows = e.reshape(BT * n, 3)
-        hyp = [v.detach().requires_grad_(True) for v in (G_lm, Bb_lm, tg_lm, tb_lm)]
-        wsel = [i for i, w in enumerate(wb) if w.requires_grad]
-        d_hyp = [torch.zeros_like(v) for v in hyp]
-        d_wb = [torch.zeros_like(w) if w.requires_grad else None for w in wb]
-        dh = torch.zeros((), device=dev, dtype=torch.float64)          # dL/dh, summed in f64 (a handful of dot products per evaluation)
-        dot = lambda u, v: (u.double() * v.double()).sum()
-        CW = (1.0 / 6.0, 2.0 / 6.0, 2.0 / 6.0, 1.0 / 6.0)              # weights of k1..k4 in the RK4 combination
-        TC = (0.0, 0.5, 0.5, 1.0)                                      # stage i: t + TC[i] h, input y + TC[i] h k_{i-1}
-        for s in range(S - 1, -1, -1):
-            k, nd = ka[s], knd[s]
-            dh += (dot(gy, k[0] + 2.0 * k[1] + 2.0 * k[2] + k[3]) + dot(glp, nd[0] + 2.0 * nd[1] + 2.0 * nd[2] + nd[3])) / 6.0
-            gy_next, g_in = gy.clone(), None                           # g_in: cotangent of the NEXT stage's input
-            for st in (3, 2, 1, 0):
-                ka_bar = (CW[st] * h) * gy
-                if g_in is not None:
-                    ka_bar = torch.addcmul(ka_bar, g_in, TC[st + 1] * h)
-                nd_bar = (CW[st] * h) * glp
-                with torch.enable_grad():
-                    t = (h * s + TC[st] * h).detach().requires_grad_(True)
-                    y_in = ys[s, st].detach().requires_grad_(True)
-                    a, nd_ = _cnf_eval_fused(wb, t, y_in, hyp[0], hyp[1], hyp[2], hyp[3], e_rows, BT, n, widths)
-                    g = torch.autograd.grad((a, nd_), [y_in, t] + hyp + [wb[i] for i in wsel], (ka_bar, nd_bar))
-                del a, nd_
-                g_in = g[0]
-                for buf, gi in zip(d_hyp, g[2:6]):
-                    buf.add_(gi)
-                for i, gi in zip(wsel, g[6:]):
-                    d_wb[i].add_(gi)
-                dh += g[1].double() * (s + TC[st])                     # through the stage time t = (s + TC) h
-                if st > 0:
-                    dh += TC[st] * dot(g_in, k[st - 1])                # through the stage input y + TC h k_{st-1}
-                gy_next.add_(g_in)
-                del g
-            gy = gy_next
+        gy, d_hyp, d_wb, dh, _ = _rk4_reverse_sweep(
+            ys, (ka, knd), gy, (glp,), h, lambda s, c, h_: h_ * s + c * h_, False,
+            lambda t, y_in, hyp, F: _cnf_eval_fused(wb, t, y_in, hyp[0], hyp[1], hyp[2], hyp[3], e_rows, F, n, widths),
+            (G_lm, Bb_lm, tg_lm, tb_lm), wb, widths)
         dt_end = (dh / S).to(t_end.dtype).reshape(t_end.shape)
         return (gy, glp, d_hyp[0], d_hyp[1], d_hyp[2], d_hyp[3], dt_end, None, None, None, None, None) + tuple(d_wb)
 
@@ -758,12 +835,20 @@ def cnf_block_train(block, x, context, logpx, e):
     t: 0 -> sqrt_end_time^2 with `block.rk4_steps` RK4 steps.  -> (x_T, logp_T), differentiable in every parameter."""
     layers = block.odefunc.diffeq.layers
     BT, n, _ = x.shape
+    fused = all(_fused_layer_ok(l, n) for l in layers[1:3])
+    # BLOCK_NODE (config.train_cnf_block_node; off by default): the whole solve as one node with a tape of (BT,n,3) tensors only
+    # (CnfBlockSolve), where the fused-layer kernels and the bf16x6 CNF kernel apply; `_block_node_used` tells tests / tools which route ran
+    block._block_node_used = bool(BLOCK_NODE and fused and ops.CNF_BF16X6 and tuple(l._layer.weight.shape[0] for l in layers) == (512, 512, 512, 3))
+    if block._block_node_used:
+        (G_lm, Bb_lm, tg_lm, tb_lm, widths), t_end, w1x, w2x, wb = _block_node_inputs(block, context, x.device)
+        y, lp = CnfBlockSolve.apply(x, logpx, G_lm, Bb_lm, tg_lm, tb_lm, t_end, e, w1x, w2x, block.rk4_steps, widths, *wb)
+        block.odefunc._num_evals.fill_(4 * block.rk4_steps)
+        return y, lp
     # hyper networks: the context columns once per solve, the time column per evaluation; layer-major 1-D tensors (_hyper_layer_major)
     G_lm, Bb_lm, tg_lm, tb_lm, widths = _hyper_layer_major(block, context)
     e_rows = e.reshape(BT * n, 3)
     # row layout of the (2R, C) tensors of this solve (include/caspr_hip_train.h): blocks of 32 value rows + the tangent rows of the
     # same points when the hidden layers run with the activation in the conv's epilogue (CnfLayer), [values | tangents] otherwise
-    fused = all(_fused_layer_ok(l, n) for l in layers[1:3])
     blk = 32 if fused else BT * n
 
     def func(t, y, _lp):
@@ -804,15 +889,6 @@ def cnf_block_train(block, x, context, logpx, e):
 
     t_end = block.sqrt_end_time * block.sqrt_end_time if block.train_T else torch.tensor(float(block.T), device=x.device)
     steps = block.rk4_steps
-    # BLOCK_NODE (config.train_cnf_block_node; off by default): the whole solve as one node with a tape of (BT,n,3) tensors only
-    # (CnfBlockSolve), where the fused-layer kernels and the bf16x6 CNF kernel apply; `_block_node_used` tells tests / tools which route ran
-    block._block_node_used = bool(BLOCK_NODE and fused and ops.CNF_BF16X6 and widths == (512, 512, 512, 3))
-    if block._block_node_used:
-        w1x, w2x = block._weights_x6()
-        wb = [p_ for l in layers for p_ in (l._layer.weight, l._layer.bias)]
-        y, lp = CnfBlockSolve.apply(x, logpx, G_lm, Bb_lm, tg_lm, tb_lm, t_end, e, w1x, w2x, steps, widths, *wb)
-        block.odefunc._num_evals.fill_(4 * steps)
-        return y, lp
     hstep = t_end / steps
     def rk4_step(t, y, lp):
         k1 = func(t, y, lp)
@@ -920,11 +996,9 @@ def _cnf_eval_value(wb, t, y, G_lm, Bb_lm, tg_lm, tb_lm, BT, n, widths):
 class CnfSampleSolve(torch.autograd.Function):
     """A CNF block's whole SAMPLING solve (RK4 from t_end down to 0, no divergence) as ONE autograd node with a tape of point-sized
     tensors: forward = one launch of caspr_cnf_sample_tape_f32, which writes the (BT,n,3) stage input and stage output of every
-    evaluation (24 bytes per point and evaluation) and no layer product; backward = the reverse sweep of CnfBlockSolve for the reversed
-    time axis -- steps S-1..0, stages 4..1, ONE evaluation rebuilt at a time from its stored stage input (_cnf_eval_value), its
-    cotangent pushed through, the results added to preallocated buffers in that fixed order (two runs give the same bits), its tape
-    dropped.  RK4 algebra by hand with h = -t_end / S and stage times t_end + (s + c_i) h; dL/dt_end through h (state update, stage
-    inputs, stage times) and through the start time, accumulated in f64.
+    evaluation (24 bytes per point and evaluation) and no layer product; backward = _rk4_reverse_sweep (see there) on the reversed
+    time axis: h = -t_end / S, stage times t_end + (s + c_i) h, the evaluation on the value-only kernels (_cnf_eval_value) with the one
+    output a, and dL/dt_end = dL/dt0 - (dL/dh) / S.
     y (BT,n,3), G_lm / Bb_lm / tg_lm / tb_lm layer-major (_hyper_layer_major), t_end 0-dim tensor, w1x / w2x (ops.pack_cnf_x6), steps,
     widths, then w0, b0, ..., w3, b3 -> x (BT,n,3)."""
 
@@ -942,46 +1016,12 @@ class CnfSampleSolve(torch.autograd.Function):
     def backward(ctx, gy):
         ys, ka, G_lm, Bb_lm, tg_lm, tb_lm, t_end = ctx.saved_tensors
         S, widths, wb = ctx.steps, ctx.widths, ctx.wb
-        _, _, BT, n, _ = ys.shape
-        dev = ys.device
-        gy = gy.contiguous()
+        n = ys.shape[3]
         t0 = t_end.detach().reshape(())
-        h = -t0 / S                                                    # reversed time axis: t_end -> 0
-        hyp = [v.detach().requires_grad_(True) for v in (G_lm, Bb_lm, tg_lm, tb_lm)]
-        wsel = [i for i, w in enumerate(wb) if w.requires_grad]
-        d_hyp = [torch.zeros_like(v) for v in hyp]
-        d_wb = [torch.zeros_like(w) if w.requires_grad else None for w in wb]
-        dh = torch.zeros((), device=dev, dtype=torch.float64)          # dL/dh and dL/d(start time), summed in f64
-        dt0 = torch.zeros((), device=dev, dtype=torch.float64)
-        dot = lambda u, v: (u.double() * v.double()).sum()
-        CW = (1.0 / 6.0, 2.0 / 6.0, 2.0 / 6.0, 1.0 / 6.0)              # weights of k1..k4 in the RK4 combination
-        TC = (0.0, 0.5, 0.5, 1.0)                                      # stage i: t_end + (s + TC[i]) h, input y + TC[i] h k_{i-1}
-        for s in range(S - 1, -1, -1):
-            k = ka[s]
-            dh += dot(gy, k[0] + 2.0 * k[1] + 2.0 * k[2] + k[3]) / 6.0
-            gy_next, g_in = gy.clone(), None                           # g_in: cotangent of the NEXT stage's input
-            for st in (3, 2, 1, 0):
-                ka_bar = (CW[st] * h) * gy
-                if g_in is not None:
-                    ka_bar = torch.addcmul(ka_bar, g_in, TC[st + 1] * h)
-                with torch.enable_grad():
-                    t = (t0 + (s + TC[st]) * h).detach().requires_grad_(True)
-                    y_in = ys[s, st].detach().requires_grad_(True)
-                    a = _cnf_eval_value(wb, t, y_in, hyp[0], hyp[1], hyp[2], hyp[3], BT, n, widths)
-                    g = torch.autograd.grad(a, [y_in, t] + hyp + [wb[i] for i in wsel], ka_bar)
-                del a
-                g_in = g[0]
-                for buf, gi in zip(d_hyp, g[2:6]):
-                    buf.add_(gi)
-                for i, gi in zip(wsel, g[6:]):
-                    d_wb[i].add_(gi)
-                dt0 += g[1].double()                                   # through the stage time t = t_end + (s + TC) h
-                dh += g[1].double() * (s + TC[st])
-                if st > 0:
-                    dh += TC[st] * dot(g_in, k[st - 1])                # through the stage input y + TC h k_{st-1}
-                gy_next.add_(g_in)
-                del g
-            gy = gy_next
+        gy, d_hyp, d_wb, dh, dt0 = _rk4_reverse_sweep(
+            ys, (ka,), gy.contiguous(), (), -t0 / S, lambda s, c, h: t0 + (s + c) * h, True,      # reversed time axis: t_end -> 0
+            lambda t, y_in, hyp, F: (_cnf_eval_value(wb, t, y_in, hyp[0], hyp[1], hyp[2], hyp[3], F, n, widths),),
+            (G_lm, Bb_lm, tg_lm, tb_lm), wb, widths)
         dt_end = (dt0 - dh / S).to(t_end.dtype).reshape(t_end.shape)   # h = -t_end / S
         return (gy, d_hyp[0], d_hyp[1], d_hyp[2], d_hyp[3], dt_end, None, None, None, None) + tuple(d_wb)
 
@@ -1012,12 +1052,10 @@ class CnfSampleSolveFrames(torch.autograd.Function):
     first (ops.cnf_steps_order), which writes frame order[p]'s tape at POSITION p, steps s < S_f only; the tape has max_f S_f step rows
     and the rows a frame did not write are never read.  The forward reads the table to the host ONCE (steps.cpu()): this route is a
     Python reverse sweep and was never capturable, so one synchronisation per solve is its price for knowing the loop bounds.
-    Backward = the sweep of CnfSampleSolve with (1) the step size and the stage times per frame -- h_f, t_f = t_end + (s + c_i) h_f, the
-    time handed to the evaluation as a layer-major vector built from an (F,) leaf, so that dL/dt_f comes back per frame; (2) at step s
-    only the first F_s = #{f : S_f > s} positions taking part: the tape, the cotangent and the hyper rows (permuted to launch order once)
-    are sliced, the value kernels run on F_s n rows, finished frames cost nothing; (3) dL/dt_end = sum_f (dt0_f - dh_f / S_f), both
-    accumulated per frame in f64.  dL/dy and the hyper gradients go back to frame order by index assignment over unique indices: no
-    atomics, two runs give the same bits.
+    Backward = _rk4_reverse_sweep (see there) as CnfSampleSolve calls it, in its per-frame form: the cotangent and the hyper rows are
+    permuted to launch order once, h_f and t_f = t_end + (s + c_i) h_f are per frame, at step s only the first F_s = #{f : S_f > s}
+    positions take part (the value kernels run on F_s n rows, finished frames cost nothing), and dL/dt_end = sum_f (dt0_f - dh_f / S_f).
+    dL/dy and the hyper gradients go back to frame order by index assignment over unique indices: no atomics, two runs give the same bits.
     y (BT,n,3), G_lm / Bb_lm / tg_lm / tb_lm layer-major, t_end 0-dim tensor, w1x / w2x, steps (BT,) int32 on y's device, max_steps (the
     largest count a frame may ask for), widths, then w0, b0, ..., w3, b3 -> x (BT,n,3)."""
 
@@ -1040,66 +1078,18 @@ class CnfSampleSolveFrames(torch.autograd.Function):
         ys, ka, G_lm, Bb_lm, tg_lm, tb_lm, t_end, order = ctx.saved_tensors
         widths, wb = ctx.widths, ctx.wb
         S_alloc, _, BT, n, _ = ys.shape
-        dev = ys.device
         pidx = order.long()                                            # position p of the launch order holds frame pidx[p]
         S_pos = [ctx.counts[f] for f in ctx.perm]                      # non-increasing
         t0 = t_end.detach().reshape(())
-        S_t = torch.tensor(S_pos, device=dev, dtype=t0.dtype)
+        S_t = torch.tensor(S_pos, device=ys.device, dtype=t0.dtype)
         h_all = -t0 / S_t                                              # (BT,) launch order: h_f = -t_end / S_f
         gy = gy.contiguous()[pidx]                                     # launch order from here on
         in_launch_order = lambda v: torch.cat([u[pidx].reshape(-1) for u in _layer_views(v.detach(), BT, widths)])
-        hyp_all = [_layer_views(in_launch_order(v), BT, widths) for v in (G_lm, Bb_lm, tg_lm, tb_lm)]
-        d_hyp = [torch.zeros_like(v) for v in (G_lm, Bb_lm, tg_lm, tb_lm)]            # launch order, layer-major over all BT frames
-        wsel = [i for i, w in enumerate(wb) if w.requires_grad]
-        d_wb = [torch.zeros_like(w) if w.requires_grad else None for w in wb]
-        dh = torch.zeros(BT, device=dev, dtype=torch.float64)          # dL/dh_f and dL/d(start time) per frame, summed in f64
-        dt0 = torch.zeros(BT, device=dev, dtype=torch.float64)
-        dots = lambda u, v: (u.double() * v.double()).flatten(1).sum(1)
-        CW = (1.0 / 6.0, 2.0 / 6.0, 2.0 / 6.0, 1.0 / 6.0)
-        TC = (0.0, 0.5, 0.5, 1.0)
-        F_cur, hyp, acc = 0, None, None
-
-        def flush():                                                   # the prefix's hyper gradients into the rows of that prefix
-            if acc is not None:
-                for buf, part in zip(d_hyp, acc):
-                    for full, pre in zip(_layer_views(buf, BT, widths), _layer_views(part, F_cur, widths)):
-                        full[:F_cur].add_(pre)
-        for s in range(S_alloc - 1, -1, -1):
-            Fs = sum(1 for c in S_pos if c > s)                        # the frames still integrating at step s: a prefix
-            if Fs != F_cur:                                            # (grows as s falls: once per distinct count)
-                flush()
-                F_cur = Fs
-                hyp = [torch.cat([u[:Fs].reshape(-1) for u in views]).requires_grad_(True) for views in hyp_all]
-                acc = [torch.zeros_like(v) for v in hyp]
-            h = h_all[:Fs].view(Fs, 1, 1)
-            g_s = gy[:Fs]
-            k = ka[s]
-            dh[:Fs] += dots(g_s, k[0, :Fs] + 2.0 * k[1, :Fs] + 2.0 * k[2, :Fs] + k[3, :Fs]) / 6.0
-            gy_next, g_in = g_s.clone(), None                          # g_in: cotangent of the NEXT stage's input
-            for st in (3, 2, 1, 0):
-                ka_bar = (CW[st] * h) * g_s
-                if g_in is not None:
-                    ka_bar = torch.addcmul(ka_bar, g_in, TC[st + 1] * h)
-                with torch.enable_grad():
-                    tF = (t0 + (s + TC[st]) * h_all[:Fs]).detach().requires_grad_(True)
-                    t = torch.cat([tF.unsqueeze(1).expand(Fs, w).reshape(-1) for w in widths])      # layer-major, as G_lm + t * tg_lm wants it
-                    y_in = ys[s, st, :Fs].detach().requires_grad_(True)
-                    a = _cnf_eval_value(wb, t, y_in, hyp[0], hyp[1], hyp[2], hyp[3], Fs, n, widths)
-                    g = torch.autograd.grad(a, [y_in, tF] + hyp + [wb[i] for i in wsel], ka_bar)
-                del a
-                g_in = g[0]
-                for buf, gi in zip(acc, g[2:6]):
-                    buf.add_(gi)
-                for i, gi in zip(wsel, g[6:]):
-                    d_wb[i].add_(gi)
-                dt0[:Fs] += g[1].double()                              # through the stage time t_f = t_end + (s + TC) h_f
-                dh[:Fs] += g[1].double() * (s + TC[st])
-                if st > 0:
-                    dh[:Fs] += TC[st] * dots(g_in, k[st - 1, :Fs])     # through the stage input y + TC h_f k_{st-1}
-                gy_next.add_(g_in)
-                del g
-            gy[:Fs] = gy_next
-        flush()
+        gy, d_hyp, d_wb, dh, dt0 = _rk4_reverse_sweep(
+            ys, (ka,), gy, (), h_all, lambda s, c, h: t0 + (s + c) * h, True,
+            lambda t, y_in, hyp, F: (_cnf_eval_value(wb, t, y_in, hyp[0], hyp[1], hyp[2], hyp[3], F, n, widths),),
+            [in_launch_order(v) for v in (G_lm, Bb_lm, tg_lm, tb_lm)], wb, widths,
+            prefix=[sum(1 for c in S_pos if c > s) for s in range(S_alloc)])      # the frames still integrating at step s
         dt_end = (dt0 - dh / S_t.double()).sum().to(t_end.dtype).reshape(t_end.shape)      # h_f = -t_end / S_f
         # back to frame order: an index assignment over the permutation (unique indices)
         dy = torch.empty_like(gy)
@@ -1118,36 +1108,23 @@ def cnf_block_sample_train(block, y, context, frame_steps=None, max_steps=None):
     context (BT,zdim) -> x (BT,n,3) at t = 0 after `block.rk4_steps` RK4 steps from sqrt_end_time^2.
     frame_steps: a (BT,) int32 tensor on y's device gives every frame its own step count, 1..max_steps (default: the kernel's limit,
     ops.CNF_MAX_TABLE_STEPS), held fixed under differentiation (CnfSampleSolveFrames); `block.rk4_steps` is not used then."""
-    if frame_steps is not None:
-        return _cnf_block_sample_train_frames(block, y, context, frame_steps, ops.CNF_MAX_TABLE_STEPS if max_steps is None else int(max_steps))
-    layers = block.odefunc.diffeq.layers
-    widths = tuple(l._layer.weight.shape[0] for l in layers)
-    if widths != (512, 512, 512, 3) or block.method != "rk4" or block.frame_steps is not None:
-        raise ValueError("the differentiable sampling solve is built for the 3-512-512-512-3 ODE function on uniform RK4 steps "
-                         "(got widths %s, method %r%s)" % (widths, block.method, ", per-frame step counts" if block.frame_steps is not None else ""))
-    G_lm, Bb_lm, tg_lm, tb_lm, widths = _hyper_layer_major(block, context)
-    t_end = block.sqrt_end_time * block.sqrt_end_time if block.train_T else torch.tensor(float(block.T), device=y.device)
-    w1x, w2x = block._weights_x6()
-    wb = [p_ for l in layers for p_ in (l._layer.weight, l._layer.bias)]
-    x = CnfSampleSolve.apply(y, G_lm, Bb_lm, tg_lm, tb_lm, t_end, w1x, w2x, block.rk4_steps, widths, *wb)
-    block.odefunc._num_evals.fill_(4 * block.rk4_steps)
-    return x
-
-
-def _cnf_block_sample_train_frames(block, y, context, frame_steps, max_steps):
-    """cnf_block_sample_train with a step table: the same block through CnfSampleSolveFrames; _num_evals = 4 max_f S_f (on the device)."""
-    layers = block.odefunc.diffeq.layers
-    widths = tuple(l._layer.weight.shape[0] for l in layers)
-    if widths != (512, 512, 512, 3) or block.method != "rk4":
-        raise ValueError("the differentiable sampling solve is built for the 3-512-512-512-3 ODE function on RK4 steps "
-                         "(got widths %s, method %r)" % (widths, block.method))
-    ops._chk_frame_table("frame_steps", frame_steps, y.shape[0], y.device)
-    G_lm, Bb_lm, tg_lm, tb_lm, widths = _hyper_layer_major(block, context)
-    t_end = block.sqrt_end_time * block.sqrt_end_time if block.train_T else torch.tensor(float(block.T), device=y.device)
-    w1x, w2x = block._weights_x6()
-    wb = [p_ for l in layers for p_ in (l._layer.weight, l._layer.bias)]
-    x = CnfSampleSolveFrames.apply(y, G_lm, Bb_lm, tg_lm, tb_lm, t_end, w1x, w2x, frame_steps, max_steps, widths, *wb)
-    block.odefunc._num_evals.copy_(4 * frame_steps.max())
+    table = frame_steps is not None
+    if table:
+        max_steps = ops.CNF_MAX_TABLE_STEPS if max_steps is None else int(max_steps)
+    widths = tuple(l._layer.weight.shape[0] for l in block.odefunc.diffeq.layers)
+    own_table = not table and block.frame_steps is not None          # the uniform route refuses a block that carries a table of its own
+    if widths != (512, 512, 512, 3) or block.method != "rk4" or own_table:
+        raise ValueError("the differentiable sampling solve is built for the 3-512-512-512-3 ODE function on %sRK4 steps (got widths %s, method %r%s)"
+                         % ("" if table else "uniform ", widths, block.method, ", per-frame step counts" if own_table else ""))
+    if table:
+        ops._chk_frame_table("frame_steps", frame_steps, y.shape[0], y.device)
+    (G_lm, Bb_lm, tg_lm, tb_lm, widths), t_end, w1x, w2x, wb = _block_node_inputs(block, context, y.device)
+    if table:
+        x = CnfSampleSolveFrames.apply(y, G_lm, Bb_lm, tg_lm, tb_lm, t_end, w1x, w2x, frame_steps, max_steps, widths, *wb)
+        block.odefunc._num_evals.copy_(4 * frame_steps.max())      # 4 max_f S_f, on the device: no host read
+    else:
+        x = CnfSampleSolve.apply(y, G_lm, Bb_lm, tg_lm, tb_lm, t_end, w1x, w2x, block.rk4_steps, widths, *wb)
+        block.odefunc._num_evals.fill_(4 * block.rk4_steps)
     return x
 
 

@@ -64,6 +64,27 @@ def _rk4(f, y, lp, h, steps, record=None):
     return y, lp
 
 
+def _fwd_restatement(BT, n, widths):
+    """caspr_cnf_train_fwd_f32 (train_ops.cnf_train_fwd) restated in plain torch for (BT, n, widths): a plain RK4 of _eval_f64 that
+    records every stage input and output.  Module level so that tools/flow_grad_diff.py can import it."""
+    cols = np.cumsum((0,) + widths)
+
+    def fwd_restatement(y, logp, e_, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_end, steps):
+        # hyper (BT, [gate l0..l3 | bias l0..l3]) and tcol as the kernel reads them -> back to layer-major
+        nG = sum(widths)
+        lm = lambda m: torch.cat([m[:, cols[l]:cols[l + 1]].reshape(-1) for l in range(4)])
+        G, Bb = lm(hyper[:, :nG]), lm(hyper[:, nG:])
+        tg, tb = lm(tcol[:nG].unsqueeze(0).expand(BT, -1)), lm(tcol[nG:].unsqueeze(0).expand(BT, -1))
+        rec = []
+        f = lambda t, y_: _eval_f64((w0, b0, w1x, b1, w2x, b2, w3, b3), t, y_, G, Bb, tg, tb, e_.reshape(-1, 3), BT, n, widths)
+        yT, lpT = _rk4(f, y, logp, t_end.reshape(()) / steps, steps, rec)
+        ys = torch.stack([torch.stack(ins) for ins, _ in rec])
+        ka = torch.stack([torch.stack([k[0] for k in ks]) for _, ks in rec])
+        knd = torch.stack([torch.stack([k[1] for k in ks]) for _, ks in rec])
+        return yT, lpT, ys, ka, knd
+    return fwd_restatement
+
+
 def test_reverse_sweep_algebra_vs_f64_autograd(monkeypatch):
     """CnfBlockSolve with caspr_cnf_train_fwd_f32 and the per-evaluation training kernels replaced by f64 torch restatements: what is
     left is the node's own arithmetic -- the hyper / tcol assembly for the kernel, the RK4 reverse algebra, the accumulation.  Every
@@ -92,20 +113,7 @@ def test_reverse_sweep_algebra_vs_f64_autograd(monkeypatch):
     e = r(BT, n, 3)
     wy, wl = r(BT, n, 3), r(BT, n, 1)
 
-    def fwd_restatement(y, logp, e_, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_end, steps):
-        # hyper (BT, [gate l0..l3 | bias l0..l3]) and tcol as the kernel reads them -> back to layer-major
-        nG = sum(widths)
-        lm = lambda m: torch.cat([m[:, cols[l]:cols[l + 1]].reshape(-1) for l in range(4)])
-        G, Bb = lm(hyper[:, :nG]), lm(hyper[:, nG:])
-        tg, tb = lm(tcol[:nG].unsqueeze(0).expand(BT, -1)), lm(tcol[nG:].unsqueeze(0).expand(BT, -1))
-        rec = []
-        f = lambda t, y_: _eval_f64((w0, b0, w1x, b1, w2x, b2, w3, b3), t, y_, G, Bb, tg, tb, e_.reshape(-1, 3), BT, n, widths)
-        yT, lpT = _rk4(f, y, logp, t_end.reshape(()) / steps, steps, rec)
-        ys = torch.stack([torch.stack(ins) for ins, _ in rec])
-        ka = torch.stack([torch.stack([k[0] for k in ks]) for _, ks in rec])
-        knd = torch.stack([torch.stack([k[1] for k in ks]) for _, ks in rec])
-        return yT, lpT, ys, ka, knd
-    monkeypatch.setattr(FG.T, "cnf_train_fwd", fwd_restatement)
+    monkeypatch.setattr(FG.T, "cnf_train_fwd", _fwd_restatement(BT, n, widths))
     monkeypatch.setattr(FG, "_cnf_eval_fused", _eval_f64)
     L = leaves_lm
     y, lp = FG.CnfBlockSolve.apply(L["x"], L["logpx"], L["G_lm"], L["Bb_lm"], L["tg_lm"], L["tb_lm"], L["t_end"], e, wbl[2], wbl[4], S, widths, *wbl)

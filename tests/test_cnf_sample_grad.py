@@ -71,6 +71,24 @@ def _rk4_down(f, y, t_end, steps, record=None):
     return y
 
 
+def _tape_restatement(BT, n, widths):
+    """caspr_cnf_sample_tape_f32 (train_ops.cnf_sample_tape) restated in plain torch for (BT, n, widths): _rk4_down of _eval_f64 that
+    records every stage input and output.  Module level so that tools/flow_grad_diff.py can import it."""
+    cols = np.cumsum((0,) + widths)
+
+    def tape_restatement(y, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_end, steps):
+        # hyper (BT, [gate l0..l3 | bias l0..l3]) and tcol as the kernel reads them -> back to layer-major
+        nG = sum(widths)
+        lm = lambda m: torch.cat([m[:, cols[l]:cols[l + 1]].reshape(-1) for l in range(4)])
+        G, Bb = lm(hyper[:, :nG]), lm(hyper[:, nG:])
+        tg, tb = lm(tcol[:nG].unsqueeze(0).expand(BT, -1)), lm(tcol[nG:].unsqueeze(0).expand(BT, -1))
+        rec = []
+        f = lambda t, y_: _eval_f64((w0, b0, w1x, b1, w2x, b2, w3, b3), t, y_, G, Bb, tg, tb, BT, n, widths)
+        x0 = _rk4_down(f, y, t_end.reshape(()), steps, rec)
+        return x0, torch.stack([torch.stack(ins) for ins, _ in rec]), torch.stack([torch.stack(ks) for _, ks in rec])
+    return tape_restatement
+
+
 def test_reverse_sweep_algebra_vs_f64_autograd(monkeypatch):
     """CnfSampleSolve with caspr_cnf_sample_tape_f32 and the per-evaluation rebuild replaced by f64 torch restatements: what is left is
     the node's own arithmetic -- the hyper / tcol assembly for the kernel, the RK4 reverse algebra on the reversed time axis, the
@@ -97,17 +115,7 @@ def test_reverse_sweep_algebra_vs_f64_autograd(monkeypatch):
     L = dict(leaves, tg_lm=over_frames(leaves["tg"]), tb_lm=over_frames(leaves["tb"]))
     wy = r(BT, n, 3)
 
-    def tape_restatement(y, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_end, steps):
-        # hyper (BT, [gate l0..l3 | bias l0..l3]) and tcol as the kernel reads them -> back to layer-major
-        nG = sum(widths)
-        lm = lambda m: torch.cat([m[:, cols[l]:cols[l + 1]].reshape(-1) for l in range(4)])
-        G, Bb = lm(hyper[:, :nG]), lm(hyper[:, nG:])
-        tg, tb = lm(tcol[:nG].unsqueeze(0).expand(BT, -1)), lm(tcol[nG:].unsqueeze(0).expand(BT, -1))
-        rec = []
-        f = lambda t, y_: _eval_f64((w0, b0, w1x, b1, w2x, b2, w3, b3), t, y_, G, Bb, tg, tb, BT, n, widths)
-        x0 = _rk4_down(f, y, t_end.reshape(()), steps, rec)
-        return x0, torch.stack([torch.stack(ins) for ins, _ in rec]), torch.stack([torch.stack(ks) for _, ks in rec])
-    monkeypatch.setattr(FG.T, "cnf_sample_tape", tape_restatement)
+    monkeypatch.setattr(FG.T, "cnf_sample_tape", _tape_restatement(BT, n, widths))
     monkeypatch.setattr(FG, "_cnf_eval_value", _eval_f64)
     x = FG.CnfSampleSolve.apply(L["y"], L["G_lm"], L["Bb_lm"], L["tg_lm"], L["tb_lm"], L["t_end"], wbl[2], wbl[4], S, widths, *wbl)
     got = torch.autograd.grad((x * wy).sum(), list(leaves.values()))

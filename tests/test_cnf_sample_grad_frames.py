@@ -96,12 +96,10 @@ def _reference_grads(BT, n, widths, leaves, wy, counts):
     return torch.cat(xs), torch.autograd.grad(loss, list(leaves.values()))
 
 
-def _node_grads(monkeypatch, BT, n, widths, leaves, wy, table, seen):
-    """CnfSampleSolveFrames with the tape launch, the order kernel and the per-evaluation rebuild replaced by f64 torch restatements."""
-    from caspr_amd.train import flow_grad as FG
+def _tape_frames_restatement(BT, n, widths, seen):
+    """caspr_cnf_sample_tape_frames_f32 (train_ops.cnf_sample_tape_frames) restated in plain torch for (BT, n, widths); appends the
+    (launch order, counts) of every call to `seen`.  Module level so that tools/flow_grad_diff.py can import it."""
     cols = np.cumsum((0,) + widths)
-    over_frames = lambda v: torch.cat([v[cols[l]:cols[l + 1]].unsqueeze(0).expand(BT, -1).reshape(-1) for l in range(4)])
-    wbl = [leaves["wb%d" % i] for i in range(8)]
 
     def tape_restatement(y, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_end, steps, max_steps, order=None, ys=None, ka=None):
         # as the kernel: position p holds frame order[p], rows s < S_f written, everything else NaN (torch.empty in the wrapper)
@@ -123,7 +121,16 @@ def _node_grads(monkeypatch, BT, n, widths, leaves, wy, table, seen):
                 ka[s, :, p] = torch.stack(ks)[:, 0]
         seen.append((perm, counts))
         return x0, ys, ka
-    monkeypatch.setattr(FG.T, "cnf_sample_tape_frames", tape_restatement)
+    return tape_restatement
+
+
+def _node_grads(monkeypatch, BT, n, widths, leaves, wy, table, seen):
+    """CnfSampleSolveFrames with the tape launch, the order kernel and the per-evaluation rebuild replaced by f64 torch restatements."""
+    from caspr_amd.train import flow_grad as FG
+    cols = np.cumsum((0,) + widths)
+    over_frames = lambda v: torch.cat([v[cols[l]:cols[l + 1]].unsqueeze(0).expand(BT, -1).reshape(-1) for l in range(4)])
+    wbl = [leaves["wb%d" % i] for i in range(8)]
+    monkeypatch.setattr(FG.T, "cnf_sample_tape_frames", _tape_frames_restatement(BT, n, widths, seen))
     monkeypatch.setattr(FG.ops, "cnf_steps_order", _order_of)
     monkeypatch.setattr(FG, "_cnf_eval_value", _eval_f64)
     x = FG.CnfSampleSolveFrames.apply(leaves["y"], leaves["G_lm"], leaves["Bb_lm"], over_frames(leaves["tg"]), over_frames(leaves["tb"]), leaves["t_end"],
