@@ -189,6 +189,7 @@ __global__ __launch_bounds__(256) void fps_kernel(const float *__restrict__ xyz,
                                                   int guard, int32_t *__restrict__ idx,
                                                   float *__restrict__ new_xyz)
 {
+    static_assert(PPT == 1 || PPT % 2 == 0, "fps_kernel: the even / odd slot permutation below drops a point for an odd PPT > 1");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *sx = smem;  // n*3
     unsigned long long *slot = reinterpret_cast<unsigned long long *>(smem + ((n * 3 + 3) & ~3));  // [2][4]
