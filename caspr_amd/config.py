@@ -18,6 +18,9 @@ class KernelConfig:
                                         # three f16 products per f32 product, n >= 128; divergence, guard check, training stay bf16x6; dopri5: cnf_dp5_split)
     cnf_dp5_split: str = "bf16x6"       # "bf16x6" | "f16x3": the operand split of the point CNF's ADAPTIVE solve (cnf_method="dopri5"; ops.CNF_DP5_SPLIT).  "f16x3":
                                         # its sampling direction (no divergence, n >= 128) on csrc/ode_dp5_f16x3w.hip; opt-in, the default keeps csrc/ode_dp5.hip
+    cnf_tape_split: str = "bf16x6"      # "bf16x6" | "f16x3": the operand split of the point CNF's sampling solve WITH THE TAPE (decode(differentiable=True), fit_latent;
+                                        # ops.CNF_TAPE_SPLIT).  "f16x3": n >= 128 on csrc/ode_sample_tape_h3w.hip, the evaluation and the bits of decode()'s own launch;
+                                        # opt-in, the default keeps csrc/ode_sample_tape.hip.  The reverse sweep is the same under both
     conv_split: str = "f16x3"           # "bf16x6" | "f16x3": the operand split of the persistent 512-channel conv in inference (ops.CONV_SPLIT; csrc/gemm_f16x3w.hip:
                                         # three f16 products per f32 product; the < 512-channel remainder, every other conv and training stay bf16x6)
     emd_route: str = "frame"            # "frame" | "rows": the forward of the approximate EMD (ops.EMD_ROUTE; csrc/emd.hip).  "frame": one workgroup per frame;
@@ -47,6 +50,7 @@ _ENV = {
     "CASPR_MATMUL": ("matmul", lambda v: v.strip().lower()),
     "CASPR_CNF_SPLIT": ("cnf_split", lambda v: v.strip().lower()),
     "CASPR_CNF_DP5_SPLIT": ("cnf_dp5_split", lambda v: v.strip().lower()),
+    "CASPR_CNF_TAPE_SPLIT": ("cnf_tape_split", lambda v: v.strip().lower()),
     "CASPR_CONV_SPLIT": ("conv_split", lambda v: v.strip().lower()),
     "CASPR_EMD_ROUTE": ("emd_route", lambda v: v.strip().lower()),
     "CASPR_CONV_X6W": ("conv_x6w", lambda v: v != "0"),
@@ -90,6 +94,8 @@ def load(environ=None):
         raise ValueError("CASPR_CNF_SPLIT must be 'bf16x6' or 'f16x3', got %r" % cfg.cnf_split)
     if cfg.cnf_dp5_split not in ("bf16x6", "f16x3"):
         raise ValueError("CASPR_CNF_DP5_SPLIT must be 'bf16x6' or 'f16x3', got %r" % cfg.cnf_dp5_split)
+    if cfg.cnf_tape_split not in ("bf16x6", "f16x3"):
+        raise ValueError("CASPR_CNF_TAPE_SPLIT must be 'bf16x6' or 'f16x3', got %r" % cfg.cnf_tape_split)
     if cfg.conv_split not in ("bf16x6", "f16x3"):
         raise ValueError("CASPR_CONV_SPLIT must be 'bf16x6' or 'f16x3', got %r" % cfg.conv_split)
     if cfg.emd_route not in ("frame", "rows"):
@@ -105,7 +111,7 @@ def active():
     from . import ops
     from .models import caspr as _c, pointnet2 as _p, tpointnet2 as _t
     d = asdict(config)
-    d.update({"matmul": ops.matmul_mode(), "cnf_split": ops.CNF_SPLIT, "cnf_dp5_split": ops.CNF_DP5_SPLIT, "conv_split": ops.CONV_SPLIT, "emd_route": ops.EMD_ROUTE, "conv_x6w": ops.CONV_X6W, "x6w_min_cin": ops._X6W_MIN_CIN, "latent_team": ops.LATENT_TEAM,
+    d.update({"matmul": ops.matmul_mode(), "cnf_split": ops.CNF_SPLIT, "cnf_dp5_split": ops.CNF_DP5_SPLIT, "cnf_tape_split": ops.CNF_TAPE_SPLIT, "conv_split": ops.CONV_SPLIT, "emd_route": ops.EMD_ROUTE, "conv_x6w": ops.CONV_X6W, "x6w_min_cin": ops._X6W_MIN_CIN, "latent_team": ops.LATENT_TEAM,
               "early_latent": _c.EARLY_LATENT, "early_latent_team": _c.EARLY_LATENT_TEAM, "sa_lo_parts": _p.LO_PARTS,
               "sa_scale_streams": _p.SCALE_STREAMS, "sa_f64_streams": _p.F64_STREAMS, "fp_commute": _p.FP_COMMUTE, "sa_pre_aggregate": _p.PRE_AGGREGATE, "global_stream": _t.GLOBAL_STREAM, "debug_env": os.environ.get("CASPR_DEBUG", "0") == "1"})
     return d

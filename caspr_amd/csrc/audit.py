@@ -1,4 +1,4 @@
-"""Code-object audit of the kernels that manage the accumulator file by hand (ode_bf16x6w.hip, its f16x3 copy ode_f16x3w.hip, the adaptive solve ode_dp5_f16x3w.hip on the same evaluation text (ode_h3w_eval.inc), gemm_bf16x6w.hip, its f16x3 copy gemm_f16x3w.hip).
+"""Code-object audit of the kernels that manage the accumulator file by hand (ode_bf16x6w.hip, its f16x3 copy ode_f16x3w.hip, the adaptive solve ode_dp5_f16x3w.hip and the taped sampling solve ode_sample_tape_h3w.hip on the same evaluation text (ode_h3w_eval.inc), gemm_bf16x6w.hip, its f16x3 copy gemm_f16x3w.hip).
 
 Both keep 256 live values at FIXED addresses a0..a255 across separate inline-asm statements.  A clobber list does not reserve
 registers between statements: what keeps hipcc out of the AGPRs is the hidden flag -amdgpu-mfma-vgpr-form (build.py EXTRA) plus the
@@ -37,9 +37,11 @@ def _code_object(obj):
     return notes, dis
 
 
-def _kernel(notes, dis, name):
+def _kernel(notes, dis, name, whole=False):
     """-> (the metadata entry of kernel `name` in the amdhsa.kernels note, its instruction list).  The note is a YAML list whose
-    entries start with "  - ." at list depth; the entry is found by its `.name:` line, not by character windows."""
+    entries start with "  - ." at list depth; the entry is found by its `.name:` line, not by character windows.  The instruction list
+    ends at the kernel's first s_endpgm; with `whole` at its LAST one in front of the next symbol (a kernel whose early return the
+    compiler gave an s_endpgm of its own in the prologue)."""
     entry, cur = None, []
     for ln in notes.splitlines() + ["  - .end"]:
         if re.match(r"^\s{0,4}- \.", ln):
@@ -53,7 +55,12 @@ def _kernel(notes, dis, name):
         raise AuditError("%s: no metadata entry in the code object's notes" % name)
     try:
         body = dis[dis.index("<%s>:" % name):]
-        body = body[:body.index("s_endpgm")]
+        if whole:
+            nxt = re.search(r"^[0-9a-f]+ <[^>]+>:$", body[1:], re.M)
+            body = body[:nxt.start() + 1] if nxt else body
+            body = body[:body.rindex("s_endpgm")]
+        else:
+            body = body[:body.index("s_endpgm")]
     except ValueError:
         raise AuditError("%s: not found in the disassembly" % name) from None
     ins = [ln.split("//")[0].strip() for ln in body.splitlines() if ln.startswith("\t")]
@@ -116,9 +123,14 @@ def audit_cnf_h3w(obj):
     regions x 6) on a[..] in the f16 form, every other MFMA in the VGPR form, M0 written by the LDS-DMA statements only (_m0_is_the_dmas).
     Also returned, not judged here: cvt_pk, the number of v_cvt_pk_f16_f32 (one per value pair and plane the kernel splits;
     tests/test_f16x3_planes_audit.py pins it)."""
+    return _audit_h3w_rk4_loop(obj, "_Z18cnf_rk4_h3w_kernel9CnfH3Args")
+
+
+def _audit_h3w_rk4_loop(obj, k, whole=False):
+    """What audit_cnf_h3w asks, of kernel `k` of `obj`: a fixed-step RK4 loop around ONE copy of the f16x3 evaluation text in the
+    instruction stream of cnf_rk4_h3w_kernel."""
     notes, dis = _code_object(obj)
-    k = "_Z18cnf_rk4_h3w_kernel9CnfH3Args"
-    meta, ins = _kernel(notes, dis, k)
+    meta, ins = _kernel(notes, dis, k, whole)
     count = lambda pat: sum(1 for i in ins if re.match(pat, i))
     _no_spills(meta, ins, k)
     _need(re.search(r"\.agpr_count:\s+256\b", meta), k + ": agpr_count != 256")
@@ -131,8 +143,16 @@ def audit_cnf_h3w(obj):
     dma = count(r"global_load_lds_dwordx4")
     m0 = _m0_is_the_dmas(ins, k)
     _need(dma > 20, "%s: %d LDS-DMA instructions" % (k, dma))
+    vgpr = re.search(r"\.vgpr_count:\s+(\d+)", meta)
     return {"kernel": k, "accvgpr_reads": r, "accvgpr_writes": w, "mfma": len(mfma), "mfma_on_acc": len(on_acc), "lds_dma": dma, "m0_writes": m0,
-            "cvt_pk": count(r"v_cvt_pk_f16_f32")}
+            "cvt_pk": count(r"v_cvt_pk_f16_f32"), "vgpr_count": int(vgpr.group(1)) if vgpr else None}
+
+
+def audit_cnf_sample_tape_h3w(obj):
+    """cnf_sample_tape_h3w_kernel (ode_sample_tape_h3w.hip: cnf_rk4_h3w_kernel's loop around the same evaluation text, with the tape
+    stores of the differentiable decode()): the contract of audit_cnf_h3w, count for count -- the tape stores are plain global stores
+    and change none of them.  Its early return (a frame with a step count of 0) has an s_endpgm of its own: the whole body is read."""
+    return _audit_h3w_rk4_loop(obj, "_Z26cnf_sample_tape_h3w_kernel19CnfSampleTapeH3Args", whole=True)
 
 
 def audit_cnf_dp5_h3w(obj):
@@ -204,7 +224,8 @@ def audit_conv_h3w(obj):
     return out
 
 
-AUDITS = {"ode_bf16x6w.hip": audit_cnf_x6w, "ode_f16x3w.hip": audit_cnf_h3w, "ode_dp5_f16x3w.hip": audit_cnf_dp5_h3w, "gemm_bf16x6w.hip": audit_conv_x6w, "gemm_f16x3w.hip": audit_conv_h3w}
+AUDITS = {"ode_bf16x6w.hip": audit_cnf_x6w, "ode_f16x3w.hip": audit_cnf_h3w, "ode_dp5_f16x3w.hip": audit_cnf_dp5_h3w, "ode_sample_tape_h3w.hip": audit_cnf_sample_tape_h3w,
+          "gemm_bf16x6w.hip": audit_conv_x6w, "gemm_f16x3w.hip": audit_conv_h3w}
 
 
 def audit_objects(objs_by_source):

@@ -6,7 +6,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.abspath(os.path.join(HERE, "..", "..")))
-SOURCES = ["point_ops.hip", "gemm.hip", "gemm_bf16x6.hip", "gemm_bf16x6w.hip", "gemm_f16x3w.hip", "sa_mlp.hip", "ode.hip", "ode_bf16x6.hip", "ode_bf16x6w.hip", "ode_f16x3w.hip", "cnf_frame_steps.hip", "ode_dp5.hip", "ode_dp5_f16x3w.hip", "ode_train_fwd.hip", "ode_sample_tape.hip", "ode_latent_dp5.hip", "backward.hip", "backward_points.hip", "backward_flow.hip", "backward_flow_value.hip", "emd.hip", "emd_exact.hip", "pose.hip", "base_sample.hip"]
+SOURCES = ["point_ops.hip", "gemm.hip", "gemm_bf16x6.hip", "gemm_bf16x6w.hip", "gemm_f16x3w.hip", "sa_mlp.hip", "ode.hip", "ode_bf16x6.hip", "ode_bf16x6w.hip", "ode_f16x3w.hip", "cnf_frame_steps.hip", "ode_dp5.hip", "ode_dp5_f16x3w.hip", "ode_train_fwd.hip", "ode_sample_tape.hip", "ode_sample_tape_h3w.hip", "ode_latent_dp5.hip", "backward.hip", "backward_points.hip", "backward_flow.hip", "backward_flow_value.hip", "emd.hip", "emd_exact.hip", "pose.hip", "base_sample.hip"]
 EXTRA = {"point_ops.hip": ["-ffp-contract=off"], "emd.hip": ["-ffp-contract=off"], "pose.hip": ["-ffp-contract=off"],
          "emd_exact.hip": ["-ffp-contract=off"],   # its f32 costs and f64 bids are restated operation by operation (tests/emd_exact_ref.py)
          "cnf_frame_steps.hip": ["-ffp-contract=off"],   # its f64 decisions are restated operation by operation (tests/frame_steps_ref.py)
@@ -22,6 +22,7 @@ EXTRA = {"point_ops.hip": ["-ffp-contract=off"], "emd.hip": ["-ffp-contract=off"
          "ode_bf16x6w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
          "ode_f16x3w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],   # the same, on f16 (ode_h3w_eval.inc)
          "ode_dp5_f16x3w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],   # ... the same text under the adaptive loop
+         "ode_sample_tape_h3w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],   # ... and under the RK4 loop that writes the tape
          "gemm_bf16x6w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
          "gemm_f16x3w.hip": ["-mllvm", "-pragma-unroll-threshold=400000", "-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"]}   # its f16x3 copy
 # CASPR_BUILD_DEBUG=1: the flavour with phase-trace hooks and experiment switches (-DCASPR_DEBUG_HOOKS, see common.h), built
@@ -95,7 +96,7 @@ def build(force=False, verbose=False):
                     raise
                 import warnings
                 warnings.warn("caspr_amd build: code-object audit FAILED and was skipped on request (CASPR_SKIP_AUDIT=1):\n%s\n"
-                              "run `pytest -m gpu` before trusting cnf_rk4_x6w_kernel / cnf_rk4_h3w_kernel / cnf_dp5_h3w_kernel / conv1x1_x6w_kernel / conv1x1_h3w_kernel" % e, RuntimeWarning)
+                              "run `pytest -m gpu` before trusting cnf_rk4_x6w_kernel / cnf_rk4_h3w_kernel / cnf_dp5_h3w_kernel / cnf_sample_tape_h3w_kernel / conv1x1_x6w_kernel / conv1x1_h3w_kernel" % e, RuntimeWarning)
         run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUT] + objs)
     return OUT
 

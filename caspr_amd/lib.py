@@ -172,6 +172,10 @@ SIGNATURES = {
                                           c_fp, c_fp, c_fp, c_int, c_int, c_stream]),
     "caspr_cnf_sample_tape_frames_f32": (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_fp, ctypes.c_void_p, c_fp, ctypes.c_void_p, c_fp, c_fp, c_fp, c_int, c_fp,
                                                  c_ip, c_int, c_ip, c_fp, c_fp, c_fp, c_int, c_int, c_stream]),
+    "caspr_cnf_sample_tape_h3_f32": (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_fp, ctypes.c_void_p, c_fp, ctypes.c_void_p, c_fp, c_fp, c_fp, c_int, c_fp, c_int,
+                                             ctypes.c_void_p, c_fp, c_fp, c_fp, c_int, c_int, c_stream]),
+    "caspr_cnf_sample_tape_h3_frames_f32": (c_int, [c_fp, c_fp, c_int, c_fp, c_fp, c_fp, ctypes.c_void_p, c_fp, ctypes.c_void_p, c_fp, c_fp, c_fp, c_int, c_fp,
+                                                    c_ip, c_int, c_ip, ctypes.c_void_p, c_fp, c_fp, c_fp, c_int, c_int, c_stream]),
     "caspr_cnf_value_splits": (c_int, [c_int]),
     "caspr_cnf_in_value_f32": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_long, c_int, c_int, c_fp, c_int, c_stream]),
     "caspr_cnf_in_value_bwd_f32": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_long, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_stream]),

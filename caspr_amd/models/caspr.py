@@ -665,7 +665,8 @@ class CaSPR(nn.Module):
         parameter of the point CNF, as the reference's decode is (caspr.py:262 through torchdiffeq): the sampling solve runs as one
         autograd node per block with a tape of (BT,n,3) tensors (train/flow_grad.py: point_cnf_sample_train; discretise-then-optimise:
         the gradient of the RK4 map itself).  Needs grad mode, GPU tensors, uniform RK4 steps (not cnf_method="dopri5", not
-        cnf_steps="frame"): otherwise a ValueError says which; no guard on this route.
+        cnf_steps="frame"): otherwise a ValueError says which; no guard on this route.  With config.cnf_tape_split = "f16x3" (opt-in) and
+        num_points >= 128 its forward launch is the f16x3 evaluation of the inference solve: per block the bits decode() itself returns.
         frame_steps (with differentiable=True only; inference has cnf_steps="frame"): None (default) = cnf_rk4_steps for every frame.  A
         (B*T,) int32 tensor on z's device = the RK4 step count of every frame, 1..cnf_steps_max; "pilot" = chosen here as the inference
         route chooses them (the pilot of cnf_steps="frame" with the model's cnf_steps_tol / _safety / _max / _points, run under no_grad;
@@ -741,6 +742,7 @@ class CaSPR(nn.Module):
         differentiable=True: the plain serial composition the reference has -- encode -> aggregate_and_solve_latent ->
         decode(differentiable=True) -- on the current stream, recorded by autograd (encoder, latent ODE and point CNF each through their
         training route); no side streams, no early latent solve, no accuracy guard.  Same return tuple; see decode() for what it needs.
+        config.cnf_tape_split = "f16x3" (opt-in) selects the forward launch of the point CNF's solve here as it does in decode().
         frame_steps (with differentiable=True only): None, a (B*T,) int32 table of RK4 step counts or "pilot", handed to decode().
         check_tol: the accuracy guard's tolerance for THIS call (default: the model's `check_tol` attribute; None = off).
         sequence_ids (device sampler only; ignored with the host sampler or a given `y`): int64 (B,), the global index of each

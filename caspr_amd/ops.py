@@ -263,6 +263,8 @@ CNF_SPLIT = _cfg.cnf_split           # "f16x3": the sampling solve (no divergenc
                                      # matmul_mode()["cnf"] says "bf16x6" for both (the family; bench.py keys its roofline block on that string)
 CNF_DP5_SPLIT = _cfg.cnf_dp5_split   # "f16x3": the ADAPTIVE solve's sampling direction (cnf_method="dopri5", no divergence, n >= 128) on csrc/ode_dp5_f16x3w.hip;
                                      # "bf16x6" (the default): csrc/ode_dp5.hip on every call.  Independent of CNF_SPLIT, whose default is "f16x3"
+CNF_TAPE_SPLIT = _cfg.cnf_tape_split   # "f16x3": the sampling solve WITH THE TAPE (train/flow_grad.py: CnfSampleSolve / CnfSampleSolveFrames, n >= 128) on
+                                     # csrc/ode_sample_tape_h3w.hip: the bits of cnf_rk4's f16x3 route; "bf16x6" (the default): csrc/ode_sample_tape.hip on every call
 
 CONV_SPLIT = _cfg.conv_split         # "f16x3": the layers of the persistent 512-channel conv on three f16 products per f32 product (csrc/gemm_f16x3w.hip),
                                      # inference only; matmul_mode()["conv"] says "bf16x6" for both (the family), the timer keys stay what they are
@@ -284,6 +286,11 @@ def conv_split():
 def cnf_dp5_split():
     """CNF_DP5_SPLIT, validated where it is read."""
     return _split_switch("CNF_DP5_SPLIT")
+
+
+def cnf_tape_split():
+    """CNF_TAPE_SPLIT, validated where it is read."""
+    return _split_switch("CNF_TAPE_SPLIT")
 
 
 def cnf_split():
@@ -1171,7 +1178,7 @@ def pack_cnf_h3(w):
 # The f16x3 solve's range guard (csrc/ode_f16x3w.hip): a hidden activation that is not finite in f16 after the 2^4 scale poisons its
 # point with NaN and sets the launch's status word (zeroed by the C entry in front of every launch, copied out behind it).
 def _cnf_h3_report(records):
-    bits = 0                                         # bit 0: cnf_rk4_h3w_kernel, bit 1: cnf_dp5_h3w_kernel (include/caspr_hip.h)
+    bits = 0                                         # 1: cnf_rk4_h3w_kernel, 2: cnf_dp5_h3w_kernel, 4: cnf_sample_tape_h3w_kernel (include/caspr_hip.h)
     for words, _ in records:
         bits |= words[0]
     if bits:
@@ -1183,6 +1190,10 @@ def _cnf_h3_report(records):
         if bits & 2:
             what.append("caspr_cnf_dopri5_h3_f32 (the adaptive solve): the affected FRAMES were retired with NaN in all of their samples.  Remedy: "
                         "cnf_dp5_split=\"bf16x6\" (caspr_amd.config.config.cnf_dp5_split / caspr_amd.ops.CNF_DP5_SPLIT)")
+        if bits & 4:
+            what.append("caspr_cnf_sample_tape_h3_f32 (the sampling solve with the tape of the differentiable decode): the samples of the affected "
+                        "points were set to NaN, their tape rows are not to be trusted.  Remedy: "
+                        "cnf_tape_split=\"bf16x6\" (caspr_amd.config.config.cnf_tape_split / caspr_amd.ops.CNF_TAPE_SPLIT)")
         raise _lib.CasprHipError("the range guard of the f16x3 point-CNF solve tripped: a hidden activation of the ODE function reached 4095, which is "
                                  "not finite in f16 after the kernel's 2^4 prescale.  " + ";  ".join(what) + ": the six-product bf16 kernel, which has "
                                  "f32's exponent range")

@@ -23,6 +23,7 @@ The three block nodes -- CnfBlockSolve (forward direction, value + divergence), 
 taping solve kernel forward and share ONE hand-written reverse sweep, _rk4_reverse_sweep, whose docstring states the RK4 algebra; a
 node's backward only describes its variant (outputs, time axis, scalar or per frame) and forms dL/dt_end from what the sweep returns.
 """
+import collections
 import functools
 import weakref
 
@@ -685,13 +686,32 @@ def _hyper_for_kernel(G_lm, Bb_lm, tg_lm, tb_lm, BT, widths):
     return hyper, tcol
 
 
-def _block_node_inputs(block, context, device):
+# the packs of one hidden layer for a sampling node under ops.CNF_TAPE_SPLIT = "f16x3": bf16x6 (ops.pack_cnf_x6) and f16x3 (ops.pack_cnf_h3)
+_SolvePacks = collections.namedtuple("_SolvePacks", "x6 h3")
+
+
+def _sample_tape_route(w1x, w2x, n):
+    """Which forward launch a sampling node takes, by the rule ops.cnf_rk4 routes inference with: the 128-point f16x3 kernel when the
+    switch is on (the packs then come as _SolvePacks) and n >= 128, the 64-point bf16x6 kernel otherwise -> (f16x3?, w1, w2)."""
+    if isinstance(w1x, _SolvePacks):
+        if n >= 128 and ops.cnf_tape_split() == "f16x3":
+            return True, w1x.h3, w2x.h3
+        return False, w1x.x6, w2x.x6
+    return False, w1x, w2x
+
+
+def _block_node_inputs(block, context, device, tape_h3=False):
     """What a block node (CnfBlockSolve, CnfSampleSolve, CnfSampleSolveFrames) takes of its block:
     -> (G_lm, Bb_lm, tg_lm, tb_lm, widths) of _hyper_layer_major, t_end (0-dim, differentiable when the block trains it), the two packed
-    512 x 512 weights of the solve kernel (w1x, w2x), and [w0, b0, ..., w3, b3]."""
+    512 x 512 weights of the solve kernel (w1x, w2x), and [w0, b0, ..., w3, b3].  tape_h3 (the two sampling nodes): with
+    ops.CNF_TAPE_SPLIT = "f16x3" w1x / w2x each come as a _SolvePacks pair that also holds the block's f16x3 pack (block._weights_h3(),
+    a cache that follows its parameters); the node's forward chooses by n (_sample_tape_route)."""
     hyper = _hyper_layer_major(block, context)
     t_end = block.sqrt_end_time * block.sqrt_end_time if block.train_T else torch.tensor(float(block.T), device=device)
     w1x, w2x = block._weights_x6()
+    if tape_h3 and ops.cnf_tape_split() == "f16x3":
+        w1h, w2h = block._weights_h3()
+        w1x, w2x = _SolvePacks(w1x, w1h), _SolvePacks(w2x, w2h)
     return hyper, t_end, w1x, w2x, [p_ for l in block.odefunc.diffeq.layers for p_ in (l._layer.weight, l._layer.bias)]
 
 
@@ -998,7 +1018,8 @@ class CnfSampleSolve(torch.autograd.Function):
     tensors: forward = one launch of caspr_cnf_sample_tape_f32, which writes the (BT,n,3) stage input and stage output of every
     evaluation (24 bytes per point and evaluation) and no layer product; backward = _rk4_reverse_sweep (see there) on the reversed
     time axis: h = -t_end / S, stage times t_end + (s + c_i) h, the evaluation on the value-only kernels (_cnf_eval_value) with the one
-    output a, and dL/dt_end = dL/dt0 - (dL/dh) / S.
+    output a, and dL/dt_end = dL/dt0 - (dL/dh) / S.  With ops.CNF_TAPE_SPLIT = "f16x3" and n >= 128 the forward launch is
+    caspr_cnf_sample_tape_h3_f32 (_sample_tape_route; w1x / w2x then come as _SolvePacks): the same tape, the bits of the inference solve.
     y (BT,n,3), G_lm / Bb_lm / tg_lm / tb_lm layer-major (_hyper_layer_major), t_end 0-dim tensor, w1x / w2x (ops.pack_cnf_x6), steps,
     widths, then w0, b0, ..., w3, b3 -> x (BT,n,3)."""
 
@@ -1007,7 +1028,9 @@ class CnfSampleSolve(torch.autograd.Function):
         BT, n, _ = y.shape
         hyper, tcol = _hyper_for_kernel(G_lm, Bb_lm, tg_lm, tb_lm, BT, widths)
         w0, b0, w1, b1, w2, b2, w3, b3 = [t_.detach().contiguous() for t_ in wb]
-        x, ys, ka = T.cnf_sample_tape(y.detach().contiguous(), hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_end.detach().reshape(1).contiguous(), steps)
+        h3, w1p, w2p = _sample_tape_route(w1x, w2x, n)
+        x, ys, ka = (T.cnf_sample_tape_h3 if h3 else T.cnf_sample_tape)(y.detach().contiguous(), hyper, tcol, w0, b0, w1p, b1, w2p, b2, w3, b3,
+                                                                        t_end.detach().reshape(1).contiguous(), steps)
         ctx.save_for_backward(ys, ka, G_lm, Bb_lm, tg_lm, tb_lm, t_end)
         ctx.steps, ctx.widths, ctx.wb = steps, widths, wb
         return x
@@ -1067,8 +1090,9 @@ class CnfSampleSolveFrames(torch.autograd.Function):
         counts, perm, order = _frames_plan(steps, max_steps)
         hyper, tcol = _hyper_for_kernel(G_lm, Bb_lm, tg_lm, tb_lm, BT, widths)
         w0, b0, w1, b1, w2, b2, w3, b3 = [t_.detach().contiguous() for t_ in wb]
-        x, ys, ka = T.cnf_sample_tape_frames(y.detach().contiguous(), hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3,
-                                             t_end.detach().reshape(1).contiguous(), steps, max(counts), order)
+        h3, w1p, w2p = _sample_tape_route(w1x, w2x, n)
+        x, ys, ka = (T.cnf_sample_tape_h3_frames if h3 else T.cnf_sample_tape_frames)(y.detach().contiguous(), hyper, tcol, w0, b0, w1p, b1, w2p, b2, w3, b3,
+                                                                                      t_end.detach().reshape(1).contiguous(), steps, max(counts), order)
         ctx.save_for_backward(ys, ka, G_lm, Bb_lm, tg_lm, tb_lm, t_end, order)
         ctx.counts, ctx.perm, ctx.widths, ctx.wb = counts, perm, widths, wb
         return x
@@ -1118,7 +1142,7 @@ def cnf_block_sample_train(block, y, context, frame_steps=None, max_steps=None):
                          % ("" if table else "uniform ", widths, block.method, ", per-frame step counts" if own_table else ""))
     if table:
         ops._chk_frame_table("frame_steps", frame_steps, y.shape[0], y.device)
-    (G_lm, Bb_lm, tg_lm, tb_lm, widths), t_end, w1x, w2x, wb = _block_node_inputs(block, context, y.device)
+    (G_lm, Bb_lm, tg_lm, tb_lm, widths), t_end, w1x, w2x, wb = _block_node_inputs(block, context, y.device, tape_h3=True)
     if table:
         x = CnfSampleSolveFrames.apply(y, G_lm, Bb_lm, tg_lm, tb_lm, t_end, w1x, w2x, frame_steps, max_steps, widths, *wb)
         block.odefunc._num_evals.copy_(4 * frame_steps.max())      # 4 max_f S_f, on the device: no host read

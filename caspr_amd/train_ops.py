@@ -264,6 +264,80 @@ def cnf_sample_tape_frames(y, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_e
     return out, ys, ka
 
 
+def _chk_sample_tape_h3(name, y, hyper, tcol, w0, b0, w1h, b1, w2h, b2, w3, b3, t_end):
+    """The argument checks the two f16x3 tape wrappers share -> (BT, n)."""
+    if y.dim() != 3 or y.shape[2] != 3:
+        raise ValueError("%s: y must be (BT,n,3), got %s" % (name, tuple(y.shape)))
+    BT, n, _ = y.shape
+    if n < 128:
+        raise ValueError("%s: n = %d is below the 128-point workgroup of the f16x3 kernel: %s is the wrapper for it" % (name, n, name.replace("_h3", "")))
+    if hyper.dim() != 2 or hyper.shape[0] != BT or hyper.stride(1) != 1 or hyper.shape[1] < 2 * (3 * 512 + 3) or tcol.numel() < 2 * (3 * 512 + 3):
+        raise ValueError("%s: hyper must be (BT, >= 3078) rows and tcol hold 3078 floats, got %s / %s" % (name, tuple(hyper.shape), tuple(tcol.shape)))
+    if tuple(w0.shape) != (512, 3) or tuple(w3.shape) != (3, 512) or b0.numel() != 512 or b1.numel() != 512 or b2.numel() != 512 or b3.numel() != 3:
+        raise ValueError("%s: the kernel is built for the 3-512-512-512-3 ODE function" % name)
+    nbytes = _lib.load().caspr_cnf_h3_packed_bytes()
+    if w1h is None or w2h is None or w1h.numel() != nbytes or w2h.numel() != nbytes or w1h.dtype != torch.uint8 or w2h.dtype != torch.uint8:
+        raise ValueError("%s: the f16x3 weight packs w1h / w2h (ops.pack_cnf_h3) are required" % name)
+    if t_end.numel() != 1 or not t_end.is_cuda:
+        raise ValueError("%s: t_end must be a one-element device tensor" % name)
+    return BT, n
+
+
+def cnf_sample_tape_h3(y, hyper, tcol, w0, b0, w1h, b1, w2h, b2, w3, b3, t_end, steps):
+    """cnf_sample_tape on the 128-point f16x3 evaluation of inference (caspr_cnf_sample_tape_h3_f32; ops.CNF_TAPE_SPLIT = "f16x3"): same
+    arguments with w1h / w2h = ops.pack_cnf_h3 in place of the bf16x6 packs, n >= 128.  x_0 is bit for bit what
+    ops.cnf_rk4(..., w1h=, w2h=, reverse=True) returns for the same inputs, the same float32 t_end and the same steps.  The range guard
+    (a point with a hidden activation of 4095 or more gets NaN in x_0) reports through ops.check_deferred_errors, as ops.cnf_rk4's.
+    -> x_0 (BT,n,3), stage inputs ys (steps,4,BT,n,3), stage outputs ka (steps,4,BT,n,3)."""
+    _chk_f32(y, hyper, tcol, w0, b0, b1, b2, w3, b3, t_end)
+    BT, n = _chk_sample_tape_h3("cnf_sample_tape_h3", y, hyper, tcol, w0, b0, w1h, b1, w2h, b2, w3, b3, t_end)
+    if steps <= 0:
+        raise ValueError("cnf_sample_tape_h3: steps must be positive")
+    dev = y.device
+    out = torch.empty(BT, n, 3, device=dev, dtype=torch.float32)
+    ys = torch.empty(steps, 4, BT, n, 3, device=dev, dtype=torch.float32)
+    ka = torch.empty(steps, 4, BT, n, 3, device=dev, dtype=torch.float32)
+    with ops._cnf_h3.on(dev) as status:
+        word = status.word
+        with ops.timed("cnf_sample_tape"):
+            _lib.check(_lib.load().caspr_cnf_sample_tape_h3_f32(_p(y), _p(hyper), hyper.stride(0), _p(tcol), _p(w0), _p(b0), _p(w1h), _p(b1), _p(w2h),
+                                                                _p(b2), _p(w3), _p(b3), 512, _p(t_end), int(steps), _p(word), _p(out), _p(ys), _p(ka),
+                                                                BT, n, _stream()), "caspr_cnf_sample_tape_h3_f32")
+        status.post(word)
+    return out, ys, ka
+
+
+def cnf_sample_tape_h3_frames(y, hyper, tcol, w0, b0, w1h, b1, w2h, b2, w3, b3, t_end, steps, max_steps, order=None, ys=None, ka=None):
+    """cnf_sample_tape_frames on the 128-point f16x3 evaluation (caspr_cnf_sample_tape_h3_frames_f32; the kernel of cnf_sample_tape_h3):
+    same arguments with w1h / w2h = ops.pack_cnf_h3, n >= 128; the tape in LAUNCH order, rows s < S_f only, ys / ka may be handed in.
+    Frame f's x_0 is bit for bit what cnf_sample_tape_h3 gives on that frame alone with S_f steps.  -> x_0 (BT,n,3), ys, ka."""
+    _chk_f32(y, hyper, tcol, w0, b0, b1, b2, w3, b3, t_end, ys, ka)
+    BT, n = _chk_sample_tape_h3("cnf_sample_tape_h3_frames", y, hyper, tcol, w0, b0, w1h, b1, w2h, b2, w3, b3, t_end)
+    ops._chk_frame_table("steps", steps, BT, y.device)
+    if order is not None:
+        ops._chk_frame_table("order", order, BT, y.device)
+    max_steps = int(max_steps)
+    if not 1 <= max_steps <= ops.CNF_MAX_TABLE_STEPS:
+        raise ValueError("cnf_sample_tape_h3_frames: max_steps must lie in 1..%d, got %d" % (ops.CNF_MAX_TABLE_STEPS, max_steps))
+    dev = y.device
+    shape = (max_steps, 4, BT, n, 3)           # max_steps is the kernel's clamp AND the tape's step rows: they must be the same number
+    for name, t in (("ys", ys), ("ka", ka)):
+        if t is not None and (tuple(t.shape) != shape or t.device != dev or not t.is_contiguous()):
+            raise ValueError("cnf_sample_tape_h3_frames: %s must be a contiguous %s tensor on %s, got %s on %s" % (name, shape, dev, tuple(t.shape), t.device))
+    out = torch.empty(BT, n, 3, device=dev, dtype=torch.float32)
+    ys = torch.empty(shape, device=dev, dtype=torch.float32) if ys is None else ys
+    ka = torch.empty(shape, device=dev, dtype=torch.float32) if ka is None else ka
+    with ops._cnf_h3.on(dev) as status:
+        word = status.word
+        with ops.timed("cnf_sample_tape"):
+            _lib.check(_lib.load().caspr_cnf_sample_tape_h3_frames_f32(_p(y), _p(hyper), hyper.stride(0), _p(tcol), _p(w0), _p(b0), _p(w1h), _p(b1),
+                                                                       _p(w2h), _p(b2), _p(w3), _p(b3), 512, _p(t_end), _p(steps), max_steps, _p(order),
+                                                                       _p(word), _p(out), _p(ys), _p(ka), BT, n, _stream()),
+                       "caspr_cnf_sample_tape_h3_frames_f32")
+        status.post(word)
+    return out, ys, ka
+
+
 # ---- the gated softplus layers on value rows only (csrc/backward_flow_value.hip): R = frames * n rows, point p in row p.
 # gate / beta (frames, C) contiguous; the backward wrappers return dgate / dbeta (frames, C) with the point splits already summed.
 # The (rows, C) tensors may hold MORE than R rows: the caller rounds the row count up (to the 128 rows the bf16x6 conv kernels want of

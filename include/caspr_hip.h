@@ -404,7 +404,9 @@ int caspr_cnf_rk4_x6_f32(const float *y_in, const float *hyper, int ldh, const f
  *   w1h / w2h  the (512,512) hidden weights packed by caspr_pack_weight_cnf_h3 (caspr_cnf_h3_packed_bytes() bytes each);
  *   status     one device word, zeroed by the entry on `stream` in front of the launch.  RANGE GUARD: a point one of whose
  *              hidden activations is not finite in f16 after the 2^4 scale (|x| >= 4095) gets NaN in its three outputs and the
- *              word is set to 1; every other point is unaffected.  The remedy is the bf16x6 entry above.
+ *              word is set to 1; every other point is unaffected.  The remedy is the bf16x6 entry above.  (The word's values by
+ *              entry: 1 caspr_cnf_rk4_h3_f32 / _frames_, 2 caspr_cnf_dopri5_h3_f32, 4 caspr_cnf_sample_tape_h3_f32 / _frames_ of
+ *              caspr_hip_train.h.)
  * Every other argument as caspr_cnf_rk4_x6_f32 without e / logp_in / logp_out; reverse takes no flag bits.               */
 long caspr_cnf_h3_packed_bytes(void);
 int caspr_pack_weight_cnf_h3(const float *w, int ldw, void *packed, void *stream);

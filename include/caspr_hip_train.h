@@ -259,6 +259,27 @@ int caspr_cnf_sample_tape_frames_f32(const float *y_in, const float *hyper, int 
                                      int H, const float *t_end, const int32_t *steps_tab, int max_steps, const int32_t *order, float *y_out,
                                      float *ys, float *ka, int BT, int n, void *stream);
 
+/* The same two solves on the 128-point f16x3 evaluation that inference runs (csrc/ode_sample_tape_h3w.hip; the Python host's
+ * config.cnf_tape_split = "f16x3"): the RK4 loop of caspr_cnf_rk4_h3_f32 (caspr_hip.h) with reverse = 1 and no MovingBatchNorm, so
+ * y_out is BIT FOR BIT what that entry returns for the same inputs, the same float32 *t_end and the same step count; ys / ka in the
+ * layout and with the meaning of caspr_cnf_sample_tape_f32 / caspr_cnf_sample_tape_frames_f32 (the tape of a frames launch in launch
+ * order, rows s >= S_f untouched).  Arguments as theirs, with
+ *   w1h / w2h  the packs of caspr_pack_weight_cnf_h3 in place of the bf16x6 packs;
+ *   status     one device word, zeroed by the entry on `stream` in front of the launch.  RANGE GUARD as caspr_cnf_rk4_h3_f32: a point
+ *              one of whose hidden activations is not finite in f16 after the 2^4 scale gets NaN in its three components of y_out and
+ *              the word gets bit value 4 (caspr_cnf_rk4_h3_f32 owns 1, caspr_cnf_dopri5_h3_f32 owns 2); its tape rows hold whatever
+ *              the arithmetic produced.  Every other point is unaffected.  The remedy is caspr_cnf_sample_tape_f32.
+ * n >= 128 (one workgroup's points): a smaller n is REFUSED -- caspr_cnf_sample_tape_f32, the 64-point kernel, is the entry for it.     */
+int caspr_cnf_sample_tape_h3_f32(const float *y_in, const float *hyper, int ldh, const float *tcol, const float *w0, const float *b0,
+                                 const void *w1h, const float *b1, const void *w2h, const float *b2, const float *w3, const float *b3,
+                                 int H, const float *t_end, int steps, unsigned *status, float *y_out, float *ys, float *ka, int BT,
+                                 int n, void *stream);
+int caspr_cnf_sample_tape_h3_frames_f32(const float *y_in, const float *hyper, int ldh, const float *tcol, const float *w0, const float *b0,
+                                        const void *w1h, const float *b1, const void *w2h, const float *b2, const float *w3,
+                                        const float *b3, int H, const float *t_end, const int32_t *steps_tab, int max_steps,
+                                        const int32_t *order, unsigned *status, float *y_out, float *ys, float *ka, int BT, int n,
+                                        void *stream);
+
 /* The gated softplus layers of the ODE function on VALUE rows only (csrc/backward_flow_value.hip), for the reverse sweep of the
  * sampling solve above (cnf.py:70-128 with logpx = None, caspr.py:262: no Hutchinson tangent, no log-density): R = frames n rows,
  * point p in row p, frame f = p / n; C % 4 == 0; b, gate, beta, Z, H, dH, dZ 16-byte aligned with row strides that are multiples

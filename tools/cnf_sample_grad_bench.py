@@ -6,10 +6,14 @@ neighbours' load: only figures of the same run compare):
     decode_grad    (b) CaSPR.decode(differentiable=True) forward + backward of a sum-of-squares loss (train/flow_grad.py: CnfSampleSolve)
     block_node     (c) the NLL-direction block node on the same tensors: CnfBlockSolve forward + backward (value AND tangent rows: twice
                    the rows of (b)), sum-of-squares loss on (x_T, logp_T)
+    decode_grad_h3 (d) as (b) with ops.CNF_TAPE_SPLIT = "f16x3": the taped forward on the 128-point f16x3 kernel (csrc/ode_sample_tape_h3w.hip),
+                   the same reverse sweep
+    tape_fwd       (e) the taped forward launch of (b) alone, on the block's own tensors: train_ops.cnf_sample_tape (64-point bf16x6)
+    tape_fwd_h3    (f) the taped forward launch of (d) alone: train_ops.cnf_sample_tape_h3 (128-point f16x3)
 
     PYTHONPATH=. timeout -k 10 600 python tools/cnf_sample_grad_bench.py [--rounds 5] [--iters 8] [--out profiles/cnf_sample_grad_bench.json]
 
-Per leg: ms per iteration of every round (device events around `iters` iterations, 8 x `iters` for the short leg (a)), their median and spread (max - min over the rounds)
+Per leg: ms per iteration of every round (device events around `iters` iterations, 8 x `iters` for the short legs (a), (e), (f)), their median and spread (max - min over the rounds)
 and torch.cuda.max_memory_allocated over a round (reset before it).  Every leg is warmed up once before the first timed round.  After the
 rounds, one more iteration of (b) and (c) each runs with the per-kernel timers on (ops.TIMING = 2): the breakdown by kernel that explains
 the ratio of the two.  The tape of (b) is not a measurement: steps x 4 x BT x n x 24 bytes."""
@@ -20,6 +24,7 @@ import numpy as np
 import torch
 
 from caspr_amd import ops
+from caspr_amd import train_ops as T
 from caspr_amd.models import CaSPR
 from caspr_amd.train import flow_grad
 from caspr_amd.utils.synthetic import seeded_state_dict
@@ -66,7 +71,31 @@ def main():
             flow_grad.BLOCK_NODE = prev
         ((xT * xT).sum() + (lp * lp).sum()).backward()
         return xT
-    legs = {"decode": leg_decode, "decode_grad": leg_decode_grad, "block_node": leg_block_node}
+
+    def leg_decode_grad_h3():
+        prev, ops.CNF_TAPE_SPLIT = ops.CNF_TAPE_SPLIT, "f16x3"
+        try:
+            return leg_decode_grad()
+        finally:
+            ops.CNF_TAPE_SPLIT = prev
+
+    # the taped forward launches alone, on what the block node hands them (train/flow_grad.py: CnfSampleSolve.forward)
+    with torch.no_grad():
+        (G_lm, Bb_lm, tg_lm, tb_lm, widths), t_end, w1x, w2x, wb = flow_grad._block_node_inputs(block, z[0], dev)
+        hyper, tcol = flow_grad._hyper_for_kernel(G_lm, Bb_lm, tg_lm, tb_lm, BT, widths)
+        w0, b0, _, b1, _, b2, w3, b3 = [t_.detach().contiguous() for t_ in wb]
+        w1h, w2h = block._weights_h3()
+        t_dev = t_end.detach().reshape(1).contiguous()
+        yb = y[0].contiguous()
+
+    def leg_tape_fwd():
+        return T.cnf_sample_tape(yb, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_dev, S)[0]
+
+    def leg_tape_fwd_h3():
+        return T.cnf_sample_tape_h3(yb, hyper, tcol, w0, b0, w1h, b1, w2h, b2, w3, b3, t_dev, S)[0]
+    legs = {"decode": leg_decode, "decode_grad": leg_decode_grad, "block_node": leg_block_node, "decode_grad_h3": leg_decode_grad_h3,
+            "tape_fwd": leg_tape_fwd, "tape_fwd_h3": leg_tape_fwd_h3}
+    short = ("decode", "tape_fwd", "tape_fwd_h3")
 
     def run(fn, iters):
         torch.cuda.synchronize()
@@ -98,11 +127,12 @@ def main():
     per = {k: {"ms": [], "peak": []} for k in legs}
     for _ in range(a.rounds):
         for k, fn in legs.items():
-            ms, peak = run(fn, a.iters * (8 if k == "decode" else 1))      # every timed window several hundred milliseconds long
+            ms, peak = run(fn, a.iters * (8 if k in short else 1))      # every timed window several hundred milliseconds long
             per[k]["ms"].append(ms)
             per[k]["peak"].append(peak)
     res = {"workload": "cfg-3 shard: BT=%d frames, n=%d points, %d RK4 steps, seeded weights; (a) decode() forward, (b) decode(differentiable=True) "
-                       "forward + backward, (c) CnfBlockSolve forward + backward on the same tensors" % (BT, n, S),
+                       "forward + backward, (c) CnfBlockSolve forward + backward on the same tensors, (d) as (b) with CNF_TAPE_SPLIT = f16x3, "
+                       "(e) / (f) the taped forward launch of (b) / (d) alone" % (BT, n, S),
            "device": torch.cuda.get_device_name(0), "rounds": a.rounds, "iters_per_round": a.iters,
            "tape_bytes_decode_grad": S * 4 * BT * n * 24, "legs": {}}
     for k in legs:
@@ -110,7 +140,12 @@ def main():
         res["legs"][k] = {"ms_median": round(float(np.median(ms)), 3), "ms_rounds": [round(v, 3) for v in ms], "spread_ms": round(max(ms) - min(ms), 3),
                           "max_memory_allocated_bytes": int(max(per[k]["peak"])), "max_memory_allocated_GB": round(max(per[k]["peak"]) / 1e9, 3)}
     res["decode_grad_over_block_node"] = round(res["legs"]["decode_grad"]["ms_median"] / res["legs"]["block_node"]["ms_median"], 4)
-    res["per_kernel_ms"] = {"decode_grad": breakdown(leg_decode_grad), "block_node": breakdown(leg_block_node)}
+    med = lambda k: res["legs"][k]["ms_median"]
+    res["tape_fwd_h3_over_tape_fwd"] = round(med("tape_fwd_h3") / med("tape_fwd"), 4)
+    res["decode_grad_h3_over_decode_grad"] = round(med("decode_grad_h3") / med("decode_grad"), 4)
+    res["x_max_abs_diff_h3_vs_bf16x6"] = float((leg_tape_fwd_h3() - leg_tape_fwd()).abs().max())
+    ops.check_deferred_errors()
+    res["per_kernel_ms"] = {"decode_grad": breakdown(leg_decode_grad), "block_node": breakdown(leg_block_node), "decode_grad_h3": breakdown(leg_decode_grad_h3)}
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:
