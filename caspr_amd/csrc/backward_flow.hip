@@ -501,3 +501,110 @@ extern "C" int caspr_cnf_out_bwd_f32(const float *dA, const float *dND, const fl
     CASPR_CHECK_LAUNCH("cnf_out_bwd");
     return CASPR_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// The same epilogue with the two RNODE integrands kept (Finlay et al. 2020: kinetic energy |f|^2 and the Hutchinson estimate of
+// |df/dy|_F^2).  The tangent rows hold J e (forward mode), so both squared norms are on chip here:
+//   a, nd        as cnf_out_fwd_kernel (same expressions, same order: the same bits)
+//   Q[p][0]  = sum_j a[p][j]^2                    Q[p][1] = sum_j (Zo[t(p)][j] gate[f][j])^2
+// backward, with da'_j = dA_j + 2 dQ0 a_j (a recomputed) and dt'_j = -dND e_j + 2 dQ1 (Zo[t][j] gate_j):
+//   dZo[v] = da' gate, dZo[t] = dt' gate, dgate = sum_p da' (Zo[v] + b) + dt' Zo[t], dbeta = sum_p da'
+// in the per-frame fixed-order sums of cnf_out_bwd_kernel.  With dQ = 0 every product above is the one cnf_out_bwd_kernel forms.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void cnf_out_reg_fwd_kernel(const float *__restrict__ Zo, int ldo, const float *__restrict__ b,
+                                                              const float *__restrict__ gate, const float *__restrict__ beta, int ldg,
+                                                              const float *__restrict__ E, long R, int n, int shift, long toff,
+                                                              float *__restrict__ A, float *__restrict__ ND, float *__restrict__ Q)
+{
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= R) return;
+    const long f = p / n, rv = cnf_vrow(p, shift), rt = rv + toff;
+    float nd = 0.f, qk = 0.f, qj = 0.f;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float g = gate[f * ldg + j];
+        const float a = (Zo[rv * ldo + j] + b[j]) * g + beta[f * ldg + j];
+        const float jt = Zo[rt * ldo + j] * g;
+        A[p * 3 + j] = a;
+        nd += jt * E[p * 3 + j];
+        qk += a * a;
+        qj += jt * jt;
+    }
+    ND[p] = -nd;
+    Q[p * 2] = qk;
+    Q[p * 2 + 1] = qj;
+}
+
+__global__ __launch_bounds__(256) void cnf_out_reg_bwd_kernel(const float *__restrict__ dA, const float *__restrict__ dND,
+                                                              const float *__restrict__ dQ, const float *__restrict__ Zo, int ldo,
+                                                              const float *__restrict__ b, const float *__restrict__ gate,
+                                                              const float *__restrict__ beta, int ldg, const float *__restrict__ E, long R,
+                                                              int n, int shift, long toff, float *__restrict__ dZo,
+                                                              float *__restrict__ dgate, float *__restrict__ dbeta)
+{
+    __shared__ float s_red[4][6];
+    const long f = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float g[3], bb[3], be[3], acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { g[j] = gate[f * ldg + j]; bb[j] = b[j]; be[j] = beta[f * ldg + j]; }
+    for (int pi = threadIdx.x; pi < n; pi += 256) {
+        const long p = f * n + pi, rv = cnf_vrow(p, shift), rt = rv + toff;
+        const float dnd = dND[p], dq0 = 2.f * dQ[p * 2], dq1 = 2.f * dQ[p * 2 + 1];
+        f32x4 dv = (f32x4){0.f, 0.f, 0.f, 0.f}, dt = dv;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float zb = Zo[rv * ldo + j] + bb[j], zt = Zo[rt * ldo + j];
+            const float da = dA[p * 3 + j] + dq0 * (zb * g[j] + be[j]);
+            const float dad = -dnd * E[p * 3 + j] + dq1 * (zt * g[j]);
+            dv[j] = da * g[j];
+            dt[j] = dad * g[j];
+            acc[j] += da * zb + dad * zt;
+            acc[3 + j] += da;
+        }
+        st4(dZo + rv * 4, dv);
+        st4(dZo + rt * 4, dt);
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) acc[k] = wave_sum_f(acc[k]);
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s_red[wave][k] = acc[k];
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        const float t = (s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + (s_red[2][threadIdx.x] + s_red[3][threadIdx.x]);
+        if (threadIdx.x < 3) dgate[f * 3 + threadIdx.x] = t;
+        else dbeta[f * 3 + threadIdx.x - 3] = t;
+    }
+}
+
+extern "C" int caspr_cnf_out_reg_f32(const float *Zo, int ldo, const float *b, const float *gate, const float *beta, int ldg, const float *E,
+                                     long R, int n, long blk, float *A, float *ND, float *Q, void *stream)
+{
+    CASPR_REQUIRE(Zo && b && gate && beta && E && A && ND && Q && R > 0 && n > 0 && R % n == 0 && ldo >= 3 && ldg >= 3,
+                  "cnf_out_reg: bad arguments");
+    const int shift = cnf_blk_shift(R, blk);
+    CASPR_REQUIRE(shift >= -1, "cnf_out_reg: blk=%ld must be R or a power of two that divides R=%ld", blk, R);
+    CASPR_REQUIRE((R + 255) / 256 <= 2147483647L, "cnf_out_reg: too many rows");
+    cnf_out_reg_fwd_kernel<<<dim3((unsigned)((R + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(Zo, ldo, b, gate, beta, ldg, E, R, n, shift, blk, A,
+                                                                                                    ND, Q);
+    CASPR_CHECK_LAUNCH("cnf_out_reg");
+    return CASPR_OK;
+}
+
+extern "C" int caspr_cnf_out_reg_bwd_f32(const float *dA, const float *dND, const float *dQ, const float *Zo, int ldo, const float *b,
+                                         const float *gate, const float *beta, int ldg, const float *E, long R, int n, long blk, float *dZo,
+                                         float *dgate, float *dbeta, void *stream)
+{
+    CASPR_REQUIRE(dA && dND && dQ && Zo && b && gate && beta && E && dZo && dgate && dbeta && R > 0 && n > 0 && R % n == 0 && ldo >= 3 &&
+                      ldg >= 3 && ((uintptr_t)dZo % 16) == 0,
+                  "cnf_out_reg_bwd: bad arguments");
+    const int shift = cnf_blk_shift(R, blk);
+    CASPR_REQUIRE(shift >= -1, "cnf_out_reg_bwd: blk=%ld must be R or a power of two that divides R=%ld", blk, R);
+    const long frames = R / n;
+    CASPR_REQUIRE(frames <= 2147483647L, "cnf_out_reg_bwd: too many frames");
+    cnf_out_reg_bwd_kernel<<<dim3((unsigned)frames), dim3(256), 0, (hipStream_t)stream>>>(dA, dND, dQ, Zo, ldo, b, gate, beta, ldg, E, R, n, shift, blk,
+                                                                                         dZo, dgate, dbeta);
+    CASPR_CHECK_LAUNCH("cnf_out_reg_bwd");
+    return CASPR_OK;
+}

@@ -157,6 +157,8 @@ SIGNATURES = {
     "caspr_cnf_act_bwd_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_long, c_int, c_int, c_long, c_fp, c_int, c_fp, c_fp, c_stream]),
     "caspr_cnf_out_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_int, c_fp, c_long, c_int, c_long, c_fp, c_fp, c_stream]),
     "caspr_cnf_out_bwd_f32": (c_int, [c_fp, c_fp, c_fp, c_int, c_fp, c_fp, c_int, c_fp, c_long, c_int, c_long, c_fp, c_fp, c_fp, c_stream]),
+    "caspr_cnf_out_reg_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_int, c_fp, c_long, c_int, c_long, c_fp, c_fp, c_fp, c_stream]),
+    "caspr_cnf_out_reg_bwd_f32": (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_int, c_fp, c_long, c_int, c_long, c_fp, c_fp, c_fp, c_stream]),
     "caspr_cnf_act_bwd_out_f32": (c_int, [c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_fp, c_int, c_long, c_int, c_int, c_long, c_fp, c_int, c_fp, c_fp, c_stream]),
     "caspr_conv1x1_cnf_act_bf16x6_f32": (c_int, [ctypes.c_void_p, c_fp, c_fp, c_fp, c_fp, c_int, c_fp, c_int, c_fp, c_int, c_int, c_int, c_int, c_int, c_stream]),
     "caspr_conv1x1_cnf_act_bwd_ws_bytes": (c_long, [c_int, c_int, c_int]),

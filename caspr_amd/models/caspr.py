@@ -170,14 +170,21 @@ class CaSPR(nn.Module):
     # class-level defaults: a model pickled before these attributes existed keeps drawing on the host
     base_sampler, base_seed, _base_draw = "host", 0, 0
     cnf_steps, cnf_steps_tol, cnf_steps_safety, cnf_steps_max, cnf_steps_points = "uniform", None, 1.2, 64, 64
+    cnf_reg = False
 
     def __init__(self, radii_list=[0.02, 0.05, 0.1, 0.2, 0.4, 0.8], local_feat_size=512, latent_feat_size=1600,
                  ode_hidden_size=512, motion_feat_size=64, pretrain_tnocs=False, augment_quad=True, augment_pairs=True,
                  cnf_blocks=1, regress_tnocs=True, *, cnf_rk4_steps=8, latent_rk4_steps=2, check_tol=1e-5, latent_check_tol=None,
                  check_action="warn", check_points=64, cnf_method="rk4", cnf_atol=1e-5, cnf_rtol=1e-5,
                  latent_method="rk4", latent_rtol=1e-3, latent_atol=1e-3, base_sampler="host", base_seed=0,
-                 cnf_steps="uniform", cnf_steps_tol=None, cnf_steps_safety=1.2, cnf_steps_max=64, cnf_steps_points=64):
+                 cnf_steps="uniform", cnf_steps_tol=None, cnf_steps_safety=1.2, cnf_steps_max=64, cnf_steps_points=64, cnf_reg=False):
         super(CaSPR, self).__init__()
+        # cnf_reg=True (opt-in, training): the differentiable forward() also returns the point CNF's kinetic and Jacobian integrals per point,
+        # (B,T,N,2) = int |f|^2 dt and int |J e|^2 dt along every trajectory (train/flow_grad.py: cnf_block_train(reg=True); Finlay et al.
+        # 2020), for train/loop.py: training_loss(kinetic_weight=, jacobian_weight=).  Under no_grad that element is None.
+        if cnf_reg and pretrain_tnocs:
+            raise ValueError("cnf_reg=True regularises the point CNF: pretrain_tnocs=True builds none")
+        self.cnf_reg = bool(cnf_reg)
         # How many RK4 steps the point CNF's SAMPLING solve (decode / reconstruct) takes.  "uniform" (default): cnf_rk4_steps for every
         # frame.  "frame": a count per frame, chosen on the device at every call by a pilot on the first cnf_steps_points samples of
         # each frame (ops.cnf_frame_steps: the ladder 1, 2, 4, .., cnf_steps_max, the guard's Richardson estimate against
@@ -247,7 +254,9 @@ class CaSPR(nn.Module):
     # ------------------------------------------------------------------------------------------
     def forward(self, x, sample_points, aggregate_points=None, e=None):
         """caspr.py:76-122.  x, sample_points (B,T,N,4) -> (recon_loss (B,T,N), tnocs_loss (B,T,N,4)).
-        `e` (B*T,N,3) optionally fixes the Hutchinson noise (odefunc.py:115-117)."""
+        `e` (B*T,N,3) optionally fixes the Hutchinson noise (odefunc.py:115-117).
+        A model built with cnf_reg=True returns a third element: the CNF's regulariser integrals (B,T,N,2) with a grad_fn on the
+        differentiable path, None under no_grad (the inference kernels do not form them)."""
         if self._differentiable(x, sample_points):
             return self._forward_train(x, sample_points, e)
         with torch.no_grad():
@@ -275,6 +284,8 @@ class CaSPR(nn.Module):
             if guard is not None:
                 self._guard_cnf_end(guard, cnf_result)
             recon_loss = self.get_nll_loss(cnf_result, B, T)
+            if self.cnf_reg:
+                return tuple([recon_loss, tnocs_loss, None])
             return tuple([recon_loss, tnocs_loss])
 
     def _differentiable(self, *inputs):
@@ -302,6 +313,9 @@ class CaSPR(nn.Module):
         z = sample_feats.reshape(B * T, self.cnf_args.zdim)
         pts = sample_points.reshape(B * T, N, 4)[:, :, :3].contiguous()
         init_logprob = torch.zeros(B * T, N, 1, device=pts.device, dtype=pts.dtype)
+        if self.cnf_reg:
+            y, delta_log_py, r = point_cnf_train(self.point_cnf, pts, z, init_logprob, e=e, reg=True)
+            return tuple([self.get_nll_loss((y, delta_log_py), B, T), tnocs_loss, r.view(B, T, N, 2)])
         cnf_result = point_cnf_train(self.point_cnf, pts, z, init_logprob, e=e)
         return tuple([self.get_nll_loss(cnf_result, B, T), tnocs_loss])
 

@@ -275,6 +275,13 @@ class SplitLayers(torch.autograd.Function):
         return cat(grads[:L]), cat(grads[L:]), None, None
 
 
+def _cnf_out_args(who, zo, b, gate, beta):
+    """The argument check CnfOut and CnfOutReg share -> b as the kernels read it."""
+    if zo.stride(1) != 1 or gate.stride(1) != 1 or beta.stride(1) != 1 or gate.stride(0) != beta.stride(0):
+        raise ValueError("%s: unit column strides and a common row stride of gate / beta are required" % who)
+    return b.detach().contiguous()
+
+
 class CnfOut(torch.autograd.Function):
     """Epilogue of the 3-channel output layer (caspr_cnf_out_f32 / _bwd_f32): zo (2R, 3) [a view of the conv's 4-wide rows], b (3),
     gate / beta (frames, 3) [column slices of the all-layer tensors: passed with their row stride], e (R, 3) ->
@@ -285,9 +292,7 @@ class CnfOut(torch.autograd.Function):
         from .. import lib as _lib
         from ..ops import _p, _stream
         R = e_rows.shape[0]
-        if zo.stride(1) != 1 or gate.stride(1) != 1 or beta.stride(1) != 1 or gate.stride(0) != beta.stride(0):
-            raise ValueError("CnfOut: unit column strides and a common row stride of gate / beta are required")
-        b = b.detach().contiguous()
+        b = _cnf_out_args("CnfOut", zo, b, gate, beta)
         a = torch.empty(R, 3, device=zo.device, dtype=torch.float32)
         nd = torch.empty(R, 1, device=zo.device, dtype=torch.float32)
         _lib.check(_lib.load().caspr_cnf_out_f32(_p(zo), zo.stride(0), _p(b), _p(gate), _p(beta), gate.stride(0), _p(e_rows), R, n, blk, _p(a), _p(nd),
@@ -309,6 +314,45 @@ class CnfOut(torch.autograd.Function):
         dbeta = torch.empty(frames, 3, device=zo.device, dtype=torch.float32)
         _lib.check(_lib.load().caspr_cnf_out_bwd_f32(_p(da), _p(dnd), _p(zo), zo.stride(0), _p(b), _p(gate), gate.stride(0), _p(e_rows), R, n, ctx.blk,
                                                      _p(dzo), _p(dgate), _p(dbeta), _stream()), "caspr_cnf_out_bwd_f32")
+        return dzo[:, :3], (gate * dbeta).sum(dim=0), dgate, dbeta, None, None, None
+
+
+class CnfOutReg(torch.autograd.Function):
+    """CnfOut with the integrands of the kinetic and Jacobian regularisers kept (caspr_cnf_out_reg_f32 / _bwd_f32; Finlay et al. 2020,
+    "How to train your neural ODE"): same arguments -> a (BT, n, 3), nd (BT, n, 1) [CnfOut's bits] and q (BT, n, 2) with
+    q[..., 0] = |a|^2 and q[..., 1] = |J e|^2.  The tangent rows of zo hold J e (forward mode), so the Jacobian term is the estimator
+    |J e|^2, not RNODE's |e^T J|^2 (reverse mode); both have expectation |J|_F^2 for e ~ N(0, I).  The backward is first order: the
+    cotangent 2 dq1 (J e) joins -dnd e on the tangent rows, which the layers' backward kernels take as any other."""
+
+    @staticmethod
+    def forward(ctx, zo, b, gate, beta, e_rows, n, blk):
+        from .. import lib as _lib
+        from ..ops import _p, _stream
+        R = e_rows.shape[0]
+        b = _cnf_out_args("CnfOutReg", zo, b, gate, beta)
+        a = torch.empty(R, 3, device=zo.device, dtype=torch.float32)
+        nd = torch.empty(R, 1, device=zo.device, dtype=torch.float32)
+        q = torch.empty(R, 2, device=zo.device, dtype=torch.float32)
+        _lib.check(_lib.load().caspr_cnf_out_reg_f32(_p(zo), zo.stride(0), _p(b), _p(gate), _p(beta), gate.stride(0), _p(e_rows), R, n, blk, _p(a),
+                                                     _p(nd), _p(q), _stream()), "caspr_cnf_out_reg_f32")
+        ctx.save_for_backward(zo, b, gate, beta, e_rows)
+        ctx.n, ctx.blk = n, blk
+        return a.view(R // n, n, 3), nd.view(R // n, n, 1), q.view(R // n, n, 2)
+
+    @staticmethod
+    def backward(ctx, da, dnd, dq):
+        from .. import lib as _lib
+        from ..ops import _p, _stream
+        zo, b, gate, beta, e_rows = ctx.saved_tensors
+        R, n = e_rows.shape[0], ctx.n
+        frames = R // n
+        da, dnd, dq = da.contiguous(), dnd.contiguous(), dq.contiguous()
+        dzo = torch.empty(2 * R, 4, device=zo.device, dtype=torch.float32)
+        dgate = torch.empty(frames, 3, device=zo.device, dtype=torch.float32)
+        dbeta = torch.empty(frames, 3, device=zo.device, dtype=torch.float32)
+        _lib.check(_lib.load().caspr_cnf_out_reg_bwd_f32(_p(da), _p(dnd), _p(dq), _p(zo), zo.stride(0), _p(b), _p(gate), _p(beta), gate.stride(0),
+                                                         _p(e_rows), R, n, ctx.blk, _p(dzo), _p(dgate), _p(dbeta), _stream()),
+                   "caspr_cnf_out_reg_bwd_f32")
         return dzo[:, :3], (gate * dbeta).sum(dim=0), dgate, dbeta, None, None, None
 
 
@@ -850,11 +894,21 @@ class CnfBlockSolve(torch.autograd.Function):
         return (gy, glp, d_hyp[0], d_hyp[1], d_hyp[2], d_hyp[3], dt_end, None, None, None, None, None) + tuple(d_wb)
 
 
-def cnf_block_train(block, x, context, logpx, e):
+def cnf_block_train(block, x, context, logpx, e, reg=False):
     """x (BT,n,3), context (BT,zdim), logpx (BT,n,1), e (BT,n,3) fixed Hutchinson noise.  Forward direction
-    t: 0 -> sqrt_end_time^2 with `block.rk4_steps` RK4 steps.  -> (x_T, logp_T), differentiable in every parameter."""
+    t: 0 -> sqrt_end_time^2 with `block.rk4_steps` RK4 steps.  -> (x_T, logp_T), differentiable in every parameter.
+    reg=True (opt-in; Finlay et al. 2020): the ODE state gains r (BT,n,2), r(0) = 0, r' = (|f|^2, |J e|^2) -- the kinetic energy and
+    the Hutchinson estimate of |df/dy|_F^2 along every trajectory, integrated by the same RK4 weights as logp -> (x_T, logp_T, r_T);
+    x_T and logp_T are the bits of reg=False.  J e is what the tangent rows carry (forward mode), so the Jacobian term is |J e|^2, not
+    RNODE's |e^T J|^2; both have expectation |J|_F^2 for e ~ N(0, I).  Taped and checkpointed routes only: the block node's one-launch
+    forward does not write J e, and reg=True with config.train_cnf_block_node raises -- whenever the switch is on, also for a shape the
+    node would not take (n no multiple of 64, no bf16x6): the answer does not depend on the batch; turn the switch off to regularise."""
     layers = block.odefunc.diffeq.layers
     BT, n, _ = x.shape
+    if reg and BLOCK_NODE:
+        raise ValueError("cnf_block_train(reg=True) does not run on the block node (config.train_cnf_block_node): its one-launch forward "
+                         "does not write J e, which the Jacobian regulariser integrates; turn that switch off (it refuses for every shape, "
+                         "also one the node would not take); config.train_cnf_checkpoint is the low-memory route that carries the regularisers")
     fused = all(_fused_layer_ok(l, n) for l in layers[1:3])
     # BLOCK_NODE (config.train_cnf_block_node; off by default): the whole solve as one node with a tape of (BT,n,3) tensors only
     # (CnfBlockSolve), where the fused-layer kernels and the bf16x6 CNF kernel apply; `_block_node_used` tells tests / tools which route ran
@@ -898,6 +952,8 @@ def cnf_block_train(block, x, context, logpx, e):
             if i < 3:
                 h = CnfAct.apply(z, l._layer.bias, gate, bias, n, blk)    # fused gate + softplus on value / tangent rows
             else:                                                         # 512 -> 3 output layer: (BT,n,3) tensors
+                if OUT_NODE and reg:                                      # ... and q = (|a|^2, |zt g|^2)
+                    return CnfOutReg.apply(z, l._layer.bias, gate, bias, e_rows, n, blk)
                 if OUT_NODE:
                     a, nd = CnfOut.apply(z, l._layer.bias, gate, bias, e_rows, n, blk)    # (zv + b) g + beta,  - sum_j zt_j g_j e_j
                 else:                                                     # the same in torch element-wise ops (A/B timing, debugging)
@@ -905,18 +961,24 @@ def cnf_block_train(block, x, context, logpx, e):
                     zz = z.view(R // blk, 2, blk, cout)
                     a = (zz[:, 0].reshape(BT, n, cout) + l._layer.bias) * gate.unsqueeze(1) + bias.unsqueeze(1)
                     nd = -((zz[:, 1].reshape(BT, n, cout) * gate.unsqueeze(1)) * e).sum(dim=-1, keepdim=True)
+                    if reg:
+                        jt = zz[:, 1].reshape(BT, n, cout) * gate.unsqueeze(1)
+                        return a, nd, torch.stack([(a * a).sum(dim=-1), (jt * jt).sum(dim=-1)], dim=-1)
         return a, nd
 
     t_end = block.sqrt_end_time * block.sqrt_end_time if block.train_T else torch.tensor(float(block.T), device=x.device)
     steps = block.rk4_steps
     hstep = t_end / steps
-    def rk4_step(t, y, lp):
+    def rk4_step(t, y, lp, r=None):
         k1 = func(t, y, lp)
         k2 = func(t + 0.5 * hstep, y + 0.5 * hstep * k1[0], lp)
         k3 = func(t + 0.5 * hstep, y + 0.5 * hstep * k2[0], lp)
         k4 = func(t + hstep, y + hstep * k3[0], lp)
-        return (y + (hstep / 6.0) * (k1[0] + 2.0 * k2[0] + 2.0 * k3[0] + k4[0]),
-                lp + (hstep / 6.0) * (k1[1] + 2.0 * k2[1] + 2.0 * k3[1] + k4[1]))
+        out = (y + (hstep / 6.0) * (k1[0] + 2.0 * k2[0] + 2.0 * k3[0] + k4[0]),
+               lp + (hstep / 6.0) * (k1[1] + 2.0 * k2[1] + 2.0 * k3[1] + k4[1]))
+        if r is None:
+            return out
+        return out + (r + (hstep / 6.0) * (k1[2] + 2.0 * k2[2] + 2.0 * k3[2] + k4[2]),)
 
     # CHECKPOINT_STEPS (config.train_cnf_checkpoint; off by default): keep only the state (y, logp) at the RK4 step boundaries and
     # recompute a step's four evaluations when the backward pass reaches it -- what the reference's adjoint does too (cnf.py:100-110:
@@ -925,26 +987,33 @@ def cnf_block_train(block, x, context, logpx, e):
     ckpt = CHECKPOINT_STEPS and torch.is_grad_enabled()
     if ckpt:
         from torch.utils.checkpoint import checkpoint
-    y, lp = x, logpx
+    state = (x, logpx, torch.zeros(BT, n, 2, device=x.device, dtype=x.dtype)) if reg else (x, logpx)
     for s in range(steps):
         t = hstep * s
-        y, lp = checkpoint(rk4_step, t, y, lp, use_reentrant=False) if ckpt else rk4_step(t, y, lp)
+        state = checkpoint(rk4_step, t, *state, use_reentrant=False) if ckpt else rk4_step(t, *state)
     block.odefunc._num_evals.fill_(4 * steps)
-    return y, lp
+    return state
 
 
-def point_cnf_train(flow, x, context, logpx, e=None):
-    """SequentialFlow in the forward (training / NLL) direction (cnf.py:33-48): [MBN, CNF x k, MBN]."""
+def point_cnf_train(flow, x, context, logpx, e=None, reg=False):
+    """SequentialFlow in the forward (training / NLL) direction (cnf.py:33-48): [MBN, CNF x k, MBN].
+    reg=True -> (x, logpx, r): r (BT,n,2) = the kinetic and Jacobian integrals of cnf_block_train(reg=True) summed over the CNF blocks
+    (the Jacobian term as |J e|^2, forward mode -- see there); the MovingBatchNorm layers contribute nothing."""
     from ..models.cnf import CNF
     if e is None:
         e = torch.randn_like(x)                                           # odefunc.py:127-128
+    r = None
     for layer in flow.chain:
         if isinstance(layer, CNF):
             layer.odefunc._e = e
-            x, logpx = cnf_block_train(layer, x, context, logpx, e)
+            if reg:
+                x, logpx, r_b = cnf_block_train(layer, x, context, logpx, e, reg=True)
+                r = r_b if r is None else r + r_b
+            else:
+                x, logpx = cnf_block_train(layer, x, context, logpx, e)
         else:
             x, logpx = layer(x, context, logpx, None, False)
-    return x, logpx
+    return (x, logpx, r) if reg else (x, logpx)
 
 
 # ---------------------------------------------------------------------------------------------

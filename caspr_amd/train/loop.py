@@ -23,14 +23,28 @@ import torch.distributed as dist
 from ..utils.sharding import shard_range
 
 
-def training_loss(losses, cnf_loss_weight, tnocs_loss_weight):
-    """(loss, cnf_loss, tnocs_loss) from CaSPR.forward's tuple (train_utils.py:131-165)."""
+def training_loss(losses, cnf_loss_weight, tnocs_loss_weight, kinetic_weight=0.0, jacobian_weight=0.0):
+    """(loss, cnf_loss, tnocs_loss) from CaSPR.forward's tuple (train_utils.py:131-165).
+    kinetic_weight / jacobian_weight (default 0: the reference's loss): a model built with cnf_reg=True returns the CNF's regulariser
+    integrals r (B,T,N,2) as a third element, and cnf_loss_weight * mean_{b,t} sum_n (kinetic_weight r[..., 0] + jacobian_weight r[..., 1])
+    joins `loss` -- the NLL's own reduction, so both weights are relative to nats per point -- but not `cnf_loss`."""
+    per_point_reg = None
     if len(losses) == 1:
         per_point_nll, per_point_tnocs = None, losses[0]
     elif len(losses) == 2:
         per_point_nll, per_point_tnocs = losses
+    elif len(losses) == 3:
+        per_point_nll, per_point_tnocs, per_point_reg = losses
+        if per_point_reg is not None and (per_point_nll is None or per_point_reg.dim() != 4 or per_point_reg.shape[-1] != 2
+                                          or per_point_reg.shape[:3] != per_point_nll.shape):
+            raise ValueError("unexpected third element of shape %s: the CNF's regulariser integrals are (B, T, N, 2) beside an NLL (B, T, N)"
+                             % (tuple(per_point_reg.shape),))
     else:
         raise ValueError("unexpected number of losses returned: %d" % len(losses))
+    regularised = kinetic_weight != 0.0 or jacobian_weight != 0.0
+    if regularised and per_point_reg is None:
+        raise ValueError("kinetic_weight / jacobian_weight need the regulariser integrals: build the model with CaSPR(cnf_reg=True) and "
+                         "call it with autograd recording (under no_grad it returns None for them)")
     ref = per_point_tnocs if per_point_tnocs is not None else per_point_nll
     loss = torch.zeros(1, device=ref.device)
     cnf_loss = tnocs_loss = torch.zeros(1, device=ref.device)
@@ -40,7 +54,18 @@ def training_loss(losses, cnf_loss_weight, tnocs_loss_weight):
     if per_point_tnocs is not None:
         tnocs_loss = tnocs_loss_weight * per_point_tnocs[:, :, :, :4].mean()
         loss = loss + tnocs_loss
+    if regularised:
+        loss = loss + cnf_loss_weight * (kinetic_weight * per_point_reg[..., 0] + jacobian_weight * per_point_reg[..., 1]).sum(2).mean()
     return loss, cnf_loss, tnocs_loss
+
+
+def regulariser_means(losses):
+    """(kinetic, jacobian) as floats: the mean over sequences and frames of the per-point regulariser integrals summed over a frame's
+    points (the NLL's reduction), for logging; (nan, nan) when the tuple carries none."""
+    if len(losses) < 3 or losses[2] is None:
+        return float('nan'), float('nan')
+    m = losses[2].detach().sum(2).mean(dim=(0, 1))
+    return float(m[0]), float(m[1])
 
 
 class GradBucket:
@@ -195,9 +220,11 @@ def broadcast_model(model, src=0):
                 off += t.numel()
 
 
-def train_step(model, optimizer, pcl_in, nocs_out, cnf_loss_weight=0.01, tnocs_loss_weight=100.0, bucket=None, e=None):
+def train_step(model, optimizer, pcl_in, nocs_out, cnf_loss_weight=0.01, tnocs_loss_weight=100.0, bucket=None, e=None,
+               kinetic_weight=0.0, jacobian_weight=0.0, reg_out=None):
     """One optimisation step on this rank's sequences (train_utils.py:120-176).  Returns the python floats
-    (loss, cnf_loss, tnocs_loss) of the local shard."""
+    (loss, cnf_loss, tnocs_loss) of the local shard.  kinetic_weight / jacobian_weight: training_loss's; reg_out (a list): receives
+    regulariser_means of this step, for logging."""
     model.train()
     if bucket is not None:
         bucket.zero()              # the gradients live in the bucket (views): zero them there, keep the views
@@ -214,7 +241,9 @@ def train_step(model, optimizer, pcl_in, nocs_out, cnf_loss_weight=0.01, tnocs_l
         optimizer.step()
         return float('nan'), float('nan'), float('nan')
     losses = model(pcl_in, nocs_out, e=e) if e is not None else model(pcl_in, nocs_out)
-    loss, cnf_loss, tnocs_loss = training_loss(losses, cnf_loss_weight, tnocs_loss_weight)
+    loss, cnf_loss, tnocs_loss = training_loss(losses, cnf_loss_weight, tnocs_loss_weight, kinetic_weight, jacobian_weight)
+    if reg_out is not None:
+        reg_out[:] = regulariser_means(losses)
     loss.backward()
     if bucket is not None:
         bucket.all_reduce_mean(weight=n_local)
@@ -234,13 +263,15 @@ def shard_batch(pcl_in, nocs_out, rank=None, world=None):
 
 
 def run_one_epoch(model, data_loader, device, optimizer, cnf_loss_weight, tnocs_loss_weight, epoch, log=print, mode='train',
-                  print_stats_every=10, bucket=None):
+                  print_stats_every=10, bucket=None, kinetic_weight=0.0, jacobian_weight=0.0):
     """train_utils.py:82-232 without the plotting: iterates `data_loader` (items: ((pcl_in, nocs_out), ...)), returns the
-    list of per-batch losses (train) or the mean loss (val / test)."""
+    list of per-batch losses (train) or the mean loss (val / test).  kinetic_weight / jacobian_weight act on the training steps
+    only (validation runs under no_grad, where the model forms no regulariser: its loss stays the reference's)."""
     if mode not in ['train', 'val', 'test']:
         raise ValueError('mode must be train, val or test')
     distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     out, wsum, nsum, bsum, bnum = [], 0.0, 0, 0.0, 0
+    reg = [] if mode == 'train' and getattr(model, 'cnf_reg', False) else None
     for i, data in enumerate(data_loader):
         pcl_in, nocs_out = data[0]
         pcl_in, nocs_out = shard_batch(pcl_in.to(device), nocs_out.to(device))
@@ -248,7 +279,8 @@ def run_one_epoch(model, data_loader, device, optimizer, cnf_loss_weight, tnocs_
         if mode == 'train':
             if n_local == 0 and not distributed:
                 continue
-            loss, cnf_l, tnocs_l = train_step(model, optimizer, pcl_in, nocs_out, cnf_loss_weight, tnocs_loss_weight, bucket)
+            loss, cnf_l, tnocs_l = train_step(model, optimizer, pcl_in, nocs_out, cnf_loss_weight, tnocs_loss_weight, bucket,
+                                              kinetic_weight=kinetic_weight, jacobian_weight=jacobian_weight, reg_out=reg)
         else:
             if n_local == 0:
                 continue            # evaluation has no collective inside the loop: the reduction happens once, below
@@ -260,7 +292,8 @@ def run_one_epoch(model, data_loader, device, optimizer, cnf_loss_weight, tnocs_
         if n_local:
             out.append(loss)
             if i % print_stats_every == 0:
-                log('%s epoch %d batch %d/%d: loss %.6f (cnf %.6f, tnocs %.6f)' % (mode, epoch, i, len(data_loader), loss, cnf_l, tnocs_l))
+                log('%s epoch %d batch %d/%d: loss %.6f (cnf %.6f, tnocs %.6f)' % (mode, epoch, i, len(data_loader), loss, cnf_l, tnocs_l)
+                    + (' kinetic %.6f jacobian %.6f' % tuple(reg) if reg else ''))
     if mode == 'train':
         return out
     # One process: the reference's number exactly -- the mean of the per-batch means (train_utils.py:226), ragged last batch
@@ -277,9 +310,11 @@ def run_one_epoch(model, data_loader, device, optimizer, cnf_loss_weight, tnocs_
 
 
 def train(model, train_loader, val_loader, device, out_dir, num_epochs, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-          cnf_loss_weight=0.01, tnocs_loss_weight=100.0, val_every=1, save_every=1, log=print, resume=None):
+          cnf_loss_weight=0.01, tnocs_loss_weight=100.0, val_every=1, save_every=1, log=print, resume=None,
+          kinetic_weight=0.0, jacobian_weight=0.0):
     """train.py:135-190: Adam, validation every `val_every` epochs with BEST checkpointing, periodic checkpoints.
-    `resume` = path of a checkpoint written by this function (model + optimizer + epoch)."""
+    `resume` = path of a checkpoint written by this function (model + optimizer + epoch).  kinetic_weight / jacobian_weight
+    (default 0; a model built with cnf_reg=True): training_loss's regulariser weights, on the training steps."""
     optimizer = torch.optim.Adam(model.parameters(), lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
     bucket = GradBucket(model.parameters())
     start, val_losses = 0, []
@@ -291,7 +326,8 @@ def train(model, train_loader, val_loader, device, out_dir, num_epochs, lr=1e-4,
     broadcast_model(model, 0)      # replicas start from rank 0's parameters and buffers, whatever each rank's seed was
     is_rank0 = not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
     for epoch in range(start, num_epochs):
-        run_one_epoch(model, train_loader, device, optimizer, cnf_loss_weight, tnocs_loss_weight, epoch, log, 'train', bucket=bucket)
+        run_one_epoch(model, train_loader, device, optimizer, cnf_loss_weight, tnocs_loss_weight, epoch, log, 'train', bucket=bucket,
+                      kinetic_weight=kinetic_weight, jacobian_weight=jacobian_weight)
         if val_loader is not None and epoch % val_every == 0:
             val = run_one_epoch(model, val_loader, device, None, cnf_loss_weight, tnocs_loss_weight, epoch, log, 'val')
             if not math.isnan(val):

@@ -189,6 +189,19 @@ int caspr_cnf_out_f32(const float *Zo, int ldo, const float *b, const float *gat
 int caspr_cnf_out_bwd_f32(const float *dA, const float *dND, const float *Zo, int ldo, const float *b, const float *gate,
                           int ldg, const float *E, long R, int n, long blk, float *dZo, float *dgate, float *dbeta,
                           void *stream);
+/* ... with the two integrands of the kinetic / Jacobian regularisers (Finlay et al. 2020) kept: the tangent rows hold J e, so with
+ *   a[p][j] = (Zo[v(p)][j] + b[j]) gate[f][j] + beta[f][j],   jt[j] = Zo[t(p)][j] gate[f][j]   (J e, not stored)
+ *   nd[p] = - sum_j jt[j] e[p][j],   Q[p][0] = sum_j a[p][j]^2,   Q[p][1] = sum_j jt[j]^2      (Q (R, 2))
+ * a and nd are the bits of caspr_cnf_out_f32.  Backward, per point (a recomputed from Zo, b, gate, beta; dQ (R, 2)):
+ *   da'_j = dA_j + 2 dQ0 a_j,   dt'_j = -dND e_j + 2 dQ1 jt_j
+ *   dZo[v][j] = da'_j gate_j,   dZo[t][j] = dt'_j gate_j                                        (2R, 4; column 3 zero)
+ *   dgate[f][j] = sum_p da'_j (Zo[v][j] + b_j) + dt'_j Zo[t][j],   dbeta[f][j] = sum_p da'_j    (fixed order, no atomics)
+ * With dQ = 0 the backward returns the bits of caspr_cnf_out_bwd_f32.                                                          */
+int caspr_cnf_out_reg_f32(const float *Zo, int ldo, const float *b, const float *gate, const float *beta, int ldg,
+                          const float *E, long R, int n, long blk, float *A, float *ND, float *Q, void *stream);
+int caspr_cnf_out_reg_bwd_f32(const float *dA, const float *dND, const float *dQ, const float *Zo, int ldo, const float *b,
+                              const float *gate, const float *beta, int ldg, const float *E, long R, int n, long blk,
+                              float *dZo, float *dgate, float *dbeta, void *stream);
 
 /* A hidden layer of the ODE function in one launch (diffeq_layers.py:83-90 + odefunc.py:98-105 on value and tangent rows):
  * Z = X W^T on the bf16x6 conv kernel (wpk: caspr_pack_weight_bf16x3 of W (Cout, Cin)), H = the gated softplus of

@@ -16,6 +16,10 @@ There is no network: the pretrained `caspr_weights_cars.pth` of BASELINE.json's 
 the box can produce -- a checkpoint that went through the whole surface (train -> save -> load -> reconstruct -> evaluate).
 
     python tools/train_and_eval.py --steps 300 --out gpurun_out/trained_report.json         (GPU; ~2 min at 300 steps)
+
+--kinetic-weight / --jacobian-weight train with the point CNF's regularisers (CaSPR(cnf_reg=True)) and record both regulariser
+means beside the loss at every step and probe; --record-regularisers records them for an unregularised run too (the other leg of a comparison).
+Without any of the three the tool does what it did before: no regulariser is formed anywhere.
 """
 import argparse
 import json
@@ -44,11 +48,17 @@ def main(argv=None, timed_steps=None):
     ap.add_argument("--no-headline", action="store_true", help="skip timing the headline call on the trained weights")
     ap.add_argument("--probe-at", default="", metavar="N1,N2", help="training steps at which the model is calibrated (tol 1e-5) and the headline call timed at the "
                     "calibrated counts, WITHOUT disturbing the run (step counts and both generators' states restored): how the flow's stiffness grows with training")
+    ap.add_argument("--kinetic-weight", type=float, default=0.0, help="weight of the CNF's kinetic-energy regulariser int |f|^2 dt (train/loop.py: training_loss)")
+    ap.add_argument("--jacobian-weight", type=float, default=0.0, help="weight of the CNF's Jacobian regulariser int |J e|^2 dt; either weight non-zero "
+                    "builds the model with cnf_reg=True")
+    ap.add_argument("--record-regularisers", action="store_true", help="build the model with cnf_reg=True also at weights 0 and record both regulariser means at "
+                    "every step and probe (a taped forward on 2 fixed sequences per probe, ~17 GB): the unregularised leg of a comparison.  At weights 0 "
+                    "the loss and every gradient keep their bits")
     args = ap.parse_args(argv)
 
     from caspr_amd import ops
     from caspr_amd.models import CaSPR
-    from caspr_amd.train.loop import train_step
+    from caspr_amd.train.loop import regulariser_means, train_step
     from caspr_amd.utils.synthetic import car_sequences, seeded_state_dict
     from caspr_amd.utils.torch_utils import load_weights
     from caspr_amd.utils import evaluations as E
@@ -56,8 +66,10 @@ def main(argv=None, timed_steps=None):
     dev = torch.device("cuda:0")
     rep = {"what": "train (HIP tier) -> checkpoint (reference format) -> load -> reconstruct / evaluate, synthetic rigid cars",
            "train": {"steps": args.steps, "batch": args.batch, "seq_len": args.seq_len, "num_pts": args.num_pts, "lr": args.lr,
-                     "cnf_loss_weight": 0.01, "tnocs_loss_weight": 100.0, "data": "caspr_amd.utils.synthetic.car_sequences, a fresh seed per step"}}
-    model = CaSPR()
+                     "cnf_loss_weight": 0.01, "tnocs_loss_weight": 100.0, "kinetic_weight": args.kinetic_weight, "jacobian_weight": args.jacobian_weight,
+                     "data": "caspr_amd.utils.synthetic.car_sequences, a fresh seed per step"}}
+    cnf_reg = args.kinetic_weight != 0.0 or args.jacobian_weight != 0.0 or args.record_regularisers
+    model = CaSPR(cnf_reg=cnf_reg)
     model.load_state_dict(seeded_state_dict(model.state_dict(), 0))
     model = model.to(dev)
 
@@ -85,6 +97,33 @@ def main(argv=None, timed_steps=None):
     probes = sorted(int(v) for v in args.probe_at.split(",") if v.strip())
     along = []
     xb_p = None
+    last = {}                 # the last training step's loss and regulariser means (probes record them beside the calibrated counts)
+    xr_p = None
+
+    def reg_means_now():
+        """Both regulariser means and the NLL of the CURRENT weights on one fixed batch and fixed noise: one taped forward in eval mode (no
+        MovingBatchNorm update, nothing is stepped), both generators' states put back.  None for a model built without cnf_reg."""
+        nonlocal xr_p
+        if not cnf_reg:
+            return None
+        cpu_rng, gpu_rng = torch.get_rng_state(), torch.cuda.get_rng_state(dev)
+        if xr_p is None:
+            xr_, spr_ = car_sequences(2, args.seq_len, args.num_pts, seed=4321)
+            g_ = torch.Generator(device=dev).manual_seed(4321)
+            xr_p = (xr_.to(dev), spr_.to(dev), torch.randn(2 * args.seq_len, args.num_pts, 3, device=dev, generator=g_))
+        mode = model.training
+        model.eval()
+        try:
+            with torch.enable_grad():
+                out = model(xr_p[0], xr_p[1], e=xr_p[2])
+            kin, jac = regulariser_means(out)
+            nll = float(out[0].detach().sum(2).mean())
+        finally:
+            model.train(mode)
+            torch.set_rng_state(cpu_rng)
+            torch.cuda.set_rng_state(gpu_rng, dev)
+        del out
+        return {"kinetic": kin, "jacobian": jac, "nll_sum_over_points": nll, "on": "2 fixed sequences, fixed noise, eval mode, training step counts"}
 
     def probe(at):
         """Calibrate the CURRENT weights and time the headline call at the calibrated counts; the training run continues as if this had not happened."""
@@ -95,6 +134,7 @@ def main(argv=None, timed_steps=None):
         keep = ([b_.rk4_steps for b_ in blocks], model.cnf_args.rk4_steps, model.latent_ode.rk4_steps, model.training)
         model.eval()
         try:
+            regs_ = reg_means_now()            # at the training step counts, before the calibration installs its own
             with torch.no_grad():
                 S_, d_, L_, ld_ = model.calibrate_rk4_steps(xe.to(dev), tol=1e-5, num_points=512, timestamps=spe[0, :, 0, 3].to(dev), latent_tol=1e-5)
                 if xb_p is None:
@@ -111,7 +151,7 @@ def main(argv=None, timed_steps=None):
                     torch.cuda.synchronize()
                     ms_ = (time.perf_counter() - t1) / 4 * 1e3
                     ops.check_deferred_errors()
-            along.append({"train_steps": at, "cnf_rk4_steps": S_, "latent_rk4_steps": L_, "cnf_step_doubling_diffs": {str(k): v for k, v in d_.items()},
+            along.append({"train_steps": at, "last_train_step": dict(last), "regulariser_means": regs_, "cnf_rk4_steps": S_, "latent_rk4_steps": L_, "cnf_step_doubling_diffs": {str(k): v for k, v in d_.items()},
                           "ms_per_step": round(ms_, 3), "sequences_per_sec": round(16e3 / ms_, 2)})
         finally:
             for b_, st_ in zip(blocks, keep[0]):
@@ -126,15 +166,21 @@ def main(argv=None, timed_steps=None):
         if step in probes:
             probe(step)
         x, sp = car_sequences(args.batch, args.seq_len, args.num_pts, seed=100000 + step * args.batch)
-        loss, cnf_l, tnocs_l = train_step(model, opt, x.to(dev), sp.to(dev))
+        regs = [] if cnf_reg else None
+        loss, cnf_l, tnocs_l = train_step(model, opt, x.to(dev), sp.to(dev), kinetic_weight=args.kinetic_weight, jacobian_weight=args.jacobian_weight,
+                                          reg_out=regs)
+        last = {"step": step, "loss": loss, "nll_per_point_sum": cnf_l, "tnocs_l1": tnocs_l}
+        if cnf_reg:
+            last["kinetic"], last["jacobian"] = regs
         if step % 10 == 0 or step == args.steps - 1:
-            curve.append({"step": step, "loss": loss, "nll_per_point_sum": cnf_l, "tnocs_l1": tnocs_l})
+            curve.append(dict(last))
             print("step %4d  loss %.5f  (cnf %.5f, tnocs %.6f)" % (step, loss, cnf_l, tnocs_l), flush=True)
     torch.cuda.synchronize()
     rep["train"]["wall_s"] = round(time.perf_counter() - t0, 2)
     rep["train"]["curve"] = curve
     rep["train"]["finite"] = all(c["loss"] == c["loss"] and abs(c["loss"]) < 1e30 for c in curve)
     rep["along_training"] = along
+    rep["regulariser_means_after"] = reg_means_now()
     ops.check_deferred_errors()
 
     # ---- checkpoint in the reference's format, loaded back as test.py / bench.py --weights load one
