@@ -150,7 +150,7 @@ class CNF(nn.Module):
             info, res = res[-1], (res[0] if logpx is None else res[:-1])
             if self._count_evals:
                 self.last_nfe_per_frame = info["nfe"]
-                self.last_dp5_kernel = info.get("kernel", "cnf_dp5_kernel<%s>" % ("false" if logpx is None else "true"))
+                self.last_dp5_kernel = info.get("kernel", ops.cnf_dp5_kernel("x6", logpx is not None))
                 self.odefunc._num_evals += info["nfe"].max().to(self.odefunc._num_evals.dtype)
             return res
         # the f16x3 split: plain sampling solves only (ops.cnf_rk4 routes).  The guard's check solve (_count_evals is False then) stays on

@@ -1185,13 +1185,13 @@ def _cnf_h3_report(records):
         # one error for everything that has arrived: each kernel whose guard tripped is named with its own remedy
         what = []
         if bits & 1:
-            what.append("caspr_cnf_rk4_h3_f32 (the fixed-step sampling solve): the samples of the affected points were set to NaN.  Remedy: "
+            what.append(_CNF_ENTRY["h3"]["rk4"] + " (the fixed-step sampling solve): the samples of the affected points were set to NaN.  Remedy: "
                         "cnf_split=\"bf16x6\" (caspr_amd.config.config.cnf_split / caspr_amd.ops.CNF_SPLIT)")
         if bits & 2:
-            what.append("caspr_cnf_dopri5_h3_f32 (the adaptive solve): the affected FRAMES were retired with NaN in all of their samples.  Remedy: "
+            what.append(_CNF_ENTRY["h3"]["dopri5"] + " (the adaptive solve): the affected FRAMES were retired with NaN in all of their samples.  Remedy: "
                         "cnf_dp5_split=\"bf16x6\" (caspr_amd.config.config.cnf_dp5_split / caspr_amd.ops.CNF_DP5_SPLIT)")
         if bits & 4:
-            what.append("caspr_cnf_sample_tape_h3_f32 (the sampling solve with the tape of the differentiable decode): the samples of the affected "
+            what.append(_CNF_ENTRY["h3"]["tape"] + " (the sampling solve with the tape of the differentiable decode): the samples of the affected "
                         "points were set to NaN, their tape rows are not to be trusted.  Remedy: "
                         "cnf_tape_split=\"bf16x6\" (caspr_amd.config.config.cnf_tape_split / caspr_amd.ops.CNF_TAPE_SPLIT)")
         raise _lib.CasprHipError("the range guard of the f16x3 point-CNF solve tripped: a hidden activation of the ODE function reached 4095, which is "
@@ -1214,6 +1214,138 @@ def _chk_frame_table(name, t, BT, device):
         raise ValueError("cnf_rk4: %s must be a contiguous int32 (BT,) tensor with BT = %d, got %s %s" % (name, BT, t.dtype, tuple(t.shape)))
 
 
+CNF_HIDDEN = 512                          # the ODE function the solve kernels are built for: 3-512-512-512-3
+CNF_HYPER = 2 * (3 * CNF_HIDDEN + 3)      # the floats of a hyper row, and of tcol, they read: [gate l0..l3 | bias l0..l3]
+CNF_H3_POINTS = 128                       # the f16x3 workgroup's point count
+
+# The route table of the point CNF ("The point CNF's route table"): the kernel family that takes a solve, and the entry of
+# each route per kind of call.  An absent cell: the kernel does not exist.  A new form of a solve is one cell here.
+_CNF_ENTRY = {
+    "f32": {"rk4": "caspr_cnf_rk4_f32"},
+    "x6": {"rk4": "caspr_cnf_rk4_x6_f32", "frames": "caspr_cnf_rk4_x6_frames_f32", "dopri5": "caspr_cnf_dopri5_f32",
+           "train_fwd": "caspr_cnf_train_fwd_f32", "tape": "caspr_cnf_sample_tape_f32", "tape_frames": "caspr_cnf_sample_tape_frames_f32"},
+    "h3": {"rk4": "caspr_cnf_rk4_h3_f32", "frames": "caspr_cnf_rk4_h3_frames_f32", "dopri5": "caspr_cnf_dopri5_h3_f32",
+           "tape": "caspr_cnf_sample_tape_h3_f32", "tape_frames": "caspr_cnf_sample_tape_h3_frames_f32"},
+}
+_CNF_DP5_WS_BYTES = {"x6": "caspr_cnf_dopri5_ws_bytes", "h3": "caspr_cnf_dopri5_h3_ws_bytes"}
+
+
+def _cnf_route(n, x6, h3, e=None, narrow=False):
+    """The kernel family that takes a solve of n points a frame: "f32" | "x6" (bf16x6, 64 points a workgroup) | "h3" (f16x3, 128 points),
+    from the packs that were handed over (x6: both of w1x / w2x; h3: both of w1h / w2h), the direction (e: the Hutchinson noise of a
+    solve with the divergence) and the narrow flag.  cnf_rk4, cnf_dopri5, the f16x3 tape wrappers (as their acceptance rule) and
+    train/flow_grad.py: _sample_tape_route (which adds its switch) all ask here.  Seven rules that read like accidents and are not:
+      1. the f16x3 route needs BOTH h3 packs, no e, not narrow (cnf_rk4 alone has the flag) and n >= 128; any other call goes where
+         it would go without them, silently, and the h3 packs' size and dtype are looked at only when the route is taken;
+      2. a step table requires the x6 packs even when the f16x3 kernel then takes the call (cnf_rk4 checks that, not this function);
+      3. CNF_NARROW is or-ed into the plain x6 entry's flags only when e is None, into the frames entry's whenever narrow;
+      4. only one of w1x / w2x is no x6: the call falls through to the f32 route, which reads w1p.data / w2p.data;
+      5. cnf_rk4 and cnf_dopri5 leave the hidden width to C, the training wrappers check the 3-512-512-512-3 shape in Python; both pass
+         w0's rows as H (_cnf_head), which is 512 behind that check;
+      6. the x6 tape wrappers do not look at their packs' dtype, the h3 ones do (_cnf_packs_ok);
+      7. cnf_dopri5 sizes its workspace inside the status scope and in front of the timer (_cnf_launch: a callable `after`), and on every
+         h3 launch the timer closes before the status word is posted."""
+    if h3 and e is None and not narrow and n >= CNF_H3_POINTS:
+        return "h3"
+    return "x6" if x6 else "f32"
+
+
+def cnf_dp5_kernel(route, divergence):
+    """The name of the Dormand-Prince kernel a route runs (the "kernel" item of cnf_dopri5's trace dict)."""
+    return "cnf_dp5_h3w_kernel" if route == "h3" else "cnf_dp5_kernel<%s>" % ("true" if divergence else "false")
+
+
+def _cnf_packs_ok(route, w1, w2):
+    """Whether w1 / w2 are the route's two hidden-layer packs (pack_cnf_h3 by size and dtype, pack_cnf_x6 by size)."""
+    if route == "h3":
+        nbytes = _lib.load().caspr_cnf_h3_packed_bytes()
+        return all(w is not None and w.numel() == nbytes and w.dtype == torch.uint8 for w in (w1, w2))
+    return w1 is not None and w2 is not None and w1.numel() == _lib.load().caspr_cnf_x6_packed_bytes() and w2.numel() == w1.numel()
+
+
+def _chk_cnf(who, y, hyper, e=None, logp=None, mbn_in=None, mbn_out=None, train=None, route="x6", steps=None):
+    """The argument checks of the CNF front-end (the dtype, device and contiguity of the f32 tensors are _chk_f32's) -> (BT, n).
+    train: None for cnf_rk4 / cnf_dopri5; (tcol, w0, b0, w1, b1, w2, b2, w3, b3, t_end) for a wrapper of the training tier, which checks
+    what those two leave to C, its packs w1 / w2 of `route`, and the device scalar t_end (with steps > 0 when `steps` is given)."""
+    if y.dim() != 3 or y.shape[2] != 3:
+        raise ValueError("%s: y must be (BT,n,3), got %s" % (who, tuple(y.shape)))
+    BT, n, _ = y.shape
+    if train is None:
+        if hyper.dim() != 2 or hyper.shape[0] != BT:
+            raise ValueError("%s: hyper has %s rows for %d frames" % (who, tuple(hyper.shape), BT))
+        if (e is None) != (logp is None):
+            raise ValueError("%s: the Hutchinson noise e and the initial log-density come together" % who)
+    if e is not None and (tuple(e.shape) != tuple(y.shape) or tuple(logp.shape) != (BT, n, 1)):
+        raise ValueError("%s: e %s / logp %s do not match y %s" % (who, tuple(e.shape), tuple(logp.shape), tuple(y.shape)))
+    for name, m_ in (("mbn_in", mbn_in), ("mbn_out", mbn_out)):
+        if m_ is not None and m_.numel() != 12:
+            raise ValueError("%s: %s must hold 12 floats [weight | bias | running_mean | running_var]" % (who, name))
+    if train is not None:
+        tcol, w0, b0, w1, b1, w2, b2, w3, b3, t_end = train
+        if _cnf_route(n, True, route == "h3") != route:
+            raise ValueError("%s: n = %d is below the %d-point workgroup of the f16x3 kernel: %s is the wrapper for it"
+                             % (who, n, CNF_H3_POINTS, who.replace("_h3", "")))
+        if hyper.dim() != 2 or hyper.shape[0] != BT or hyper.stride(1) != 1 or hyper.shape[1] < CNF_HYPER or tcol.numel() < CNF_HYPER:
+            raise ValueError("%s: hyper must be (BT, >= %d) rows and tcol hold %d floats, got %s / %s"
+                             % (who, CNF_HYPER, CNF_HYPER, tuple(hyper.shape), tuple(tcol.shape)))
+        if (tuple(w0.shape) != (CNF_HIDDEN, 3) or tuple(w3.shape) != (3, CNF_HIDDEN) or b0.numel() != CNF_HIDDEN or b1.numel() != CNF_HIDDEN
+                or b2.numel() != CNF_HIDDEN or b3.numel() != 3):
+            raise ValueError("%s: the kernel is built for the 3-%d-%d-%d-3 ODE function" % (who, CNF_HIDDEN, CNF_HIDDEN, CNF_HIDDEN))
+        if not _cnf_packs_ok(route, w1, w2):
+            raise ValueError("%s: the %s (ops.pack_cnf_%s) are required"
+                             % (who, "f16x3 weight packs w1h / w2h" if route == "h3" else "bf16x6 weight packs w1x / w2x", route))
+        if t_end.numel() != 1 or not t_end.is_cuda or (steps is not None and steps <= 0):
+            raise ValueError("%s: t_end must be a one-element device tensor%s" % (who, "" if steps is None else " and steps positive"))
+    return BT, n
+
+
+def _cnf_step_table(who, y, steps, order, max_steps, tape=None):
+    """The checks of a per-frame step table (steps, order: (BT,) int32 on y's device; max_steps in 1..4096, None = 4096) -> max_steps, and
+    with tape = (ys, ka), what a *_frames tape wrapper was handed or None: -> max_steps, ys, ka, checked or allocated."""
+    BT, n, _ = y.shape
+    _chk_frame_table("steps", steps, BT, y.device)
+    if order is not None:
+        _chk_frame_table("order", order, BT, y.device)
+    max_steps = CNF_MAX_TABLE_STEPS if max_steps is None else int(max_steps)
+    if not 1 <= max_steps <= CNF_MAX_TABLE_STEPS:
+        raise ValueError("%s: max_steps must lie in 1..%d, got %d" % (who, CNF_MAX_TABLE_STEPS, max_steps))
+    if tape is None:
+        return max_steps
+    shape = (max_steps, 4, BT, n, 3)           # max_steps is the kernel's clamp AND the tape's step rows: they must be the same number
+    for name, t in zip(("ys", "ka"), tape):
+        if t is not None and (tuple(t.shape) != shape or t.device != y.device or not t.is_contiguous()):
+            raise ValueError("%s: %s must be a contiguous %s tensor on %s, got %s on %s" % (who, name, shape, y.device, tuple(t.shape), t.device))
+    return (max_steps, *(torch.empty(shape, device=y.device, dtype=torch.float32) if t is None else t for t in tape))
+
+
+def _cnf_head(y, hyper, tcol, w0, b0, w1, b1, w2, b2, w3, b3):
+    """The thirteen arguments every CNF entry begins with; w1 / w2: the hidden layers' weights in the route's form."""
+    return (_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1), _p(b1), _p(w2), _p(b2), _p(w3), _p(b3), w0.shape[0])
+
+
+@contextlib.contextmanager
+def _cnf_h3_launch(device):
+    """with _cnf_h3_launch(device) as word: <launch an f16x3 solve that reports into word>  -- reports an earlier launch's trip first and
+    posts the word behind this one (not under stream capture)."""
+    with _cnf_h3.on(device) as status:
+        word = status.word
+        yield _p(word)
+        status.post(word)
+
+
+def _cnf_launch(route, kind, timer, device, head, before, after):
+    """The one launch site: entry _CNF_ENTRY[route][kind] on (head, before[, the f16x3 status word], after, stream) under timed(timer).
+    The word's place is the C ABI's and differs by kind -- behind mbn_out (rk4, frames, dopri5), behind the step arguments (tape,
+    tape_frames) -- always in front of the result: the caller cuts its arguments there.  A callable `after` is called inside the status
+    scope and in front of the timer (cnf_dopri5 sizes its workspace there)."""
+    name = _CNF_ENTRY[route][kind]
+    entry = getattr(_lib.load(), name)
+    with _cnf_h3_launch(device) if route == "h3" else contextlib.nullcontext() as word:
+        after = after() if callable(after) else after
+        with timed(timer):
+            _lib.check(entry(*head, *before, *(() if word is None else (word,)), *after, _stream()), name)
+
+
 def cnf_rk4(y, hyper, tcol, w0, b0, w1p, b1, w2p, b2, w3, b3, t_end, steps, reverse, mbn_in=None, mbn_out=None,
             e=None, logp=None, w1x=None, w2x=None, narrow=False, w1h=None, w2h=None, order=None, max_steps=None, out=None):
     """Fixed-step RK4 of one CNF block (cnf.py:70-128).  y (BT,n,3); hyper (BT,ldh).  Returns x or (x, logp).
@@ -1228,78 +1360,32 @@ def cnf_rk4(y, hyper, tcol, w0, b0, w1p, b1, w2p, b2, w3, b3, t_end, steps, reve
     the result does not depend on it).  Frame f's rows equal, bit for bit, a call on that frame alone with its count.  out (with a
     table only): a contiguous f32 tensor of y's shape to write into -- the rows of skipped frames keep what it holds."""
     _chk_f32(y, hyper, tcol, w0, b0, b1, b2, w3, b3, mbn_in, mbn_out, e, logp)
-    BT, n, _ = y.shape
+    BT, n = _chk_cnf("cnf_rk4", y, hyper, e, logp, mbn_in, mbn_out)
+    x6 = w1x is not None and w2x is not None
     table = torch.is_tensor(steps)
     if table:
         if e is not None or logp is not None:
             raise ValueError("cnf_rk4: a step table is for the sampling direction only (no e / logp)")
-        if w1x is None or w2x is None:
+        if not x6:
             raise ValueError("cnf_rk4: a step table needs the bf16x6 weight packs w1x / w2x (pack_cnf_x6)")
-        _chk_frame_table("steps", steps, BT, y.device)
-        if order is not None:
-            _chk_frame_table("order", order, BT, y.device)
-        max_steps = CNF_MAX_TABLE_STEPS if max_steps is None else int(max_steps)
-        if not 1 <= max_steps <= CNF_MAX_TABLE_STEPS:
-            raise ValueError("cnf_rk4: max_steps must lie in 1..%d, got %d" % (CNF_MAX_TABLE_STEPS, max_steps))
+        max_steps = _cnf_step_table("cnf_rk4", y, steps, order, max_steps)
         if out is not None:
             _chk_f32(out)
             if tuple(out.shape) != tuple(y.shape) or out.device != y.device:
                 raise ValueError("cnf_rk4: out %s on %s does not match y %s on %s" % (tuple(out.shape), out.device, tuple(y.shape), y.device))
     elif order is not None or max_steps is not None or out is not None:
         raise ValueError("cnf_rk4: order / max_steps / out come with a step table (steps as a (BT,) int32 tensor)")
-    if y.dim() != 3 or y.shape[2] != 3:
-        raise ValueError("cnf_rk4: y must be (BT,n,3), got %s" % (tuple(y.shape),))
-    if hyper.dim() != 2 or hyper.shape[0] != BT:
-        raise ValueError("cnf_rk4: hyper has %s rows for %d frames" % (tuple(hyper.shape), BT))
-    if (e is None) != (logp is None):
-        raise ValueError("cnf_rk4: the Hutchinson noise e and the initial log-density come together")
-    if e is not None and (tuple(e.shape) != tuple(y.shape) or tuple(logp.shape) != (BT, n, 1)):
-        raise ValueError("cnf_rk4: e %s / logp %s do not match y %s" % (tuple(e.shape), tuple(logp.shape), tuple(y.shape)))
-    for name, m_ in (("mbn_in", mbn_in), ("mbn_out", mbn_out)):
-        if m_ is not None and m_.numel() != 12:
-            raise ValueError("cnf_rk4: %s must hold 12 floats [weight | bias | running_mean | running_var]" % name)
+    route = _cnf_route(n, x6, w1h is not None and w2h is not None, e, narrow)
+    if route == "h3" and not _cnf_packs_ok(route, w1h, w2h):
+        raise ValueError("cnf_rk4: w1h / w2h must be the packs of pack_cnf_h3")
+    w1, w2 = (w1h, w2h) if route == "h3" else (w1x, w2x) if route == "x6" else (w1p.data, w2p.data)
     out = torch.empty_like(y) if out is None else out
     lp_out = torch.empty(BT, n, 1, device=y.device, dtype=torch.float32) if e is not None else None
-    if w1h is not None and w2h is not None and e is None and not narrow and n >= 128:
-        nbytes = _lib.load().caspr_cnf_h3_packed_bytes()
-        if w1h.numel() != nbytes or w2h.numel() != nbytes or w1h.dtype != torch.uint8 or w2h.dtype != torch.uint8:
-            raise ValueError("cnf_rk4: w1h / w2h must be the packs of pack_cnf_h3")
-        with _cnf_h3.on(y.device) as status:
-            word = status.word
-            with timed("cnf_rk4"):
-                if table:
-                    _lib.check(_lib.load().caspr_cnf_rk4_h3_frames_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1h), _p(b1), _p(w2h),
-                                                                       _p(b2), _p(w3), _p(b3), w0.shape[0], float(t_end), int(bool(reverse)),
-                                                                       _p(mbn_in), _p(mbn_out), _p(word), _p(out), BT, n, _p(steps), max_steps, _p(order),
-                                                                       _stream()), "caspr_cnf_rk4_h3_frames_f32")
-                else:
-                    _lib.check(_lib.load().caspr_cnf_rk4_h3_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1h), _p(b1), _p(w2h),
-                                                                _p(b2), _p(w3), _p(b3), w0.shape[0], float(t_end), int(steps), int(bool(reverse)),
-                                                                _p(mbn_in), _p(mbn_out), _p(word), _p(out), BT, n, _stream()),
-                               "caspr_cnf_rk4_h3_f32")
-            status.post(word)
-        return out
-    if table:
-        with timed("cnf_rk4"):
-            _lib.check(_lib.load().caspr_cnf_rk4_x6_frames_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1x), _p(b1), _p(w2x),
-                                                               _p(b2), _p(w3), _p(b3), w0.shape[0], float(t_end),
-                                                               int(bool(reverse)) | (CNF_NARROW if narrow else 0), _p(mbn_in), _p(mbn_out),
-                                                               _p(out), BT, n, _p(steps), max_steps, _p(order), _stream()),
-                       "caspr_cnf_rk4_x6_frames_f32")
-        return out
-    if w1x is not None and w2x is not None:
-        with timed("cnf_rk4"):
-            _lib.check(_lib.load().caspr_cnf_rk4_x6_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1x), _p(b1), _p(w2x),
-                                                        _p(b2), _p(w3), _p(b3), w0.shape[0], float(t_end), int(steps),
-                                                        int(bool(reverse)) | (CNF_NARROW if (narrow and e is None) else 0),
-                                                        _p(mbn_in), _p(mbn_out), _p(e), _p(logp), _p(lp_out), _p(out), BT, n, _stream()),
-                       "caspr_cnf_rk4_x6_f32")
-        return out if e is None else (out, lp_out)
-    with timed("cnf_rk4"):
-        _lib.check(_lib.load().caspr_cnf_rk4_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1p.data), _p(b1),
-                                                 _p(w2p.data), _p(b2), _p(w3), _p(b3), w0.shape[0], float(t_end), int(steps), int(bool(reverse)),
-                                                 _p(mbn_in), _p(mbn_out), _p(e), _p(logp), _p(lp_out), _p(out), BT, n, _stream()),
-                   "caspr_cnf_rk4_f32")
+    flags = int(bool(reverse)) | (CNF_NARROW if narrow and route == "x6" and (table or e is None) else 0)
+    _cnf_launch(route, "frames" if table else "rk4", "cnf_rk4", y.device, _cnf_head(y, hyper, tcol, w0, b0, w1, b1, w2, b2, w3, b3),
+                (float(t_end), *(() if table else (int(steps),)), flags, _p(mbn_in), _p(mbn_out)),
+                (*(() if table or route == "h3" else (_p(e), _p(logp), _p(lp_out))), _p(out), BT, n,
+                 *((_p(steps), max_steps, _p(order)) if table else ())))
     return out if e is None else (out, lp_out)
 
 
@@ -1399,18 +1485,7 @@ def cnf_dopri5(y, hyper, tcol, w0, b0, b1, b2, w3, b3, w1x, w2x, t_end, rtol, at
     The host reads one device word per attempt: not usable under stream capture or with autograd (training keeps RK4).
     Raises CasprHipError when a frame has not reached t_end after max_attempts attempts."""
     _chk_f32(y, hyper, tcol, w0, b0, b1, b2, w3, b3, mbn_in, mbn_out, e, logp)
-    if y.dim() != 3 or y.shape[2] != 3:
-        raise ValueError("cnf_dopri5: y must be (BT,n,3), got %s" % (tuple(y.shape),))
-    BT, n, _ = y.shape
-    if hyper.dim() != 2 or hyper.shape[0] != BT:
-        raise ValueError("cnf_dopri5: hyper has %s rows for %d frames" % (tuple(hyper.shape), BT))
-    if (e is None) != (logp is None):
-        raise ValueError("cnf_dopri5: the Hutchinson noise e and the initial log-density come together")
-    if e is not None and (tuple(e.shape) != tuple(y.shape) or tuple(logp.shape) != (BT, n, 1)):
-        raise ValueError("cnf_dopri5: e %s / logp %s do not match y %s" % (tuple(e.shape), tuple(logp.shape), tuple(y.shape)))
-    for name, m_ in (("mbn_in", mbn_in), ("mbn_out", mbn_out)):
-        if m_ is not None and m_.numel() != 12:
-            raise ValueError("cnf_dopri5: %s must hold 12 floats [weight | bias | running_mean | running_var]" % name)
+    BT, n = _chk_cnf("cnf_dopri5", y, hyper, e, logp, mbn_in, mbn_out)
     if w1x is None or w2x is None:
         raise ValueError("cnf_dopri5: the bf16x6 weight packs w1x / w2x (pack_cnf_x6) are required")
     rtol, atol, max_attempts = float(rtol), float(atol), int(max_attempts)
@@ -1428,28 +1503,17 @@ def cnf_dopri5(y, hyper, tcol, w0, b0, b1, b2, w3, b3, w1x, w2x, t_end, rtol, at
     lp_out = torch.empty(BT, n, 1, device=y.device, dtype=torch.float32) if e is not None else None
     trace = torch.empty(BT, DP5_TRACE_HEAD + DP5_TRACE_ROW * max_attempts, device=y.device, dtype=torch.float32)
     counters = torch.empty(BT, 4, device=y.device, dtype=torch.int32)
-    L = _lib.load()
-    h3 = w1h is not None and w2h is not None and e is None and n >= 128
-    if h3:
-        nbytes = L.caspr_cnf_h3_packed_bytes()
-        if w1h.numel() != nbytes or w2h.numel() != nbytes or w1h.dtype != torch.uint8 or w2h.dtype != torch.uint8:
-            raise ValueError("cnf_dopri5: w1h / w2h must be the packs of pack_cnf_h3")
-        with _cnf_h3.on(y.device) as status:
-            word = status.word
-            ws = _workspace(L.caspr_cnf_dopri5_h3_ws_bytes(BT, n, max_attempts), y.device)
-            with timed("cnf_dopri5"):
-                _lib.check(L.caspr_cnf_dopri5_h3_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1h), _p(b1), _p(w2h), _p(b2), _p(w3),
-                                                     _p(b3), w0.shape[0], float(t_end), rtol, atol, max_attempts, int(bool(reverse)), _p(mbn_in),
-                                                     _p(mbn_out), _p(word), _p(out), BT, n, _p(ws), ws.numel(), _p(trace), _p(counters), _stream()),
-                           "caspr_cnf_dopri5_h3_f32")
-            status.post(word)
-    else:
-        ws = _workspace(L.caspr_cnf_dopri5_ws_bytes(BT, n, max_attempts), y.device)
-        with timed("cnf_dopri5"):
-            _lib.check(L.caspr_cnf_dopri5_f32(_p(y), _p(hyper), hyper.shape[1], _p(tcol), _p(w0), _p(b0), _p(w1x), _p(b1), _p(w2x), _p(b2), _p(w3), _p(b3),
-                                              w0.shape[0], float(t_end), rtol, atol, max_attempts, int(bool(reverse)), _p(mbn_in), _p(mbn_out),
-                                              _p(e), _p(logp), _p(lp_out), _p(out), BT, n, _p(ws), ws.numel(), _p(trace), _p(counters), _stream()),
-                       "caspr_cnf_dopri5_f32")
+    route = _cnf_route(n, True, w1h is not None and w2h is not None, e)
+    if route == "h3" and not _cnf_packs_ok(route, w1h, w2h):
+        raise ValueError("cnf_dopri5: w1h / w2h must be the packs of pack_cnf_h3")
+    w1, w2 = (w1h, w2h) if route == "h3" else (w1x, w2x)
+
+    def after():
+        ws = _workspace(getattr(_lib.load(), _CNF_DP5_WS_BYTES[route])(BT, n, max_attempts), y.device)
+        return (*(() if route == "h3" else (_p(e), _p(logp), _p(lp_out))), _p(out), BT, n, _p(ws), ws.numel(), _p(trace), _p(counters))
+
+    _cnf_launch(route, "dopri5", "cnf_dopri5", y.device, _cnf_head(y, hyper, tcol, w0, b0, w1, b1, w2, b2, w3, b3),
+                (float(t_end), rtol, atol, max_attempts, int(bool(reverse)), _p(mbn_in), _p(mbn_out)), after)
     res = (out,) if e is None else (out, lp_out)
     if return_trace:
         info = {"d0": trace[:, 0], "d1": trace[:, 1], "d2": trace[:, 2], "h0": trace[:, 3], "dt0": trace[:, 4],
@@ -1457,7 +1521,7 @@ def cnf_dopri5(y, hyper, tcol, w0, b0, b1, b2, w3, b3, w1x, w2x, t_end, rtol, at
                 "accepted": counters[:, 0], "rejected": counters[:, 1], "nfe": counters[:, 2]}
         if w1h is not None and w2h is not None:
             info["finished"] = counters[:, 3]
-            info["kernel"] = "cnf_dp5_h3w_kernel" if h3 else "cnf_dp5_kernel<%s>" % ("true" if e is not None else "false")
+            info["kernel"] = cnf_dp5_kernel(route, e is not None)
         res = res + (info,)
     return res[0] if len(res) == 1 else res
 

@@ -735,10 +735,11 @@ _SolvePacks = collections.namedtuple("_SolvePacks", "x6 h3")
 
 
 def _sample_tape_route(w1x, w2x, n):
-    """Which forward launch a sampling node takes, by the rule ops.cnf_rk4 routes inference with: the 128-point f16x3 kernel when the
-    switch is on (the packs then come as _SolvePacks) and n >= 128, the 64-point bf16x6 kernel otherwise -> (f16x3?, w1, w2)."""
+    """Which forward launch a sampling node takes, by the rule ops.cnf_rk4 routes inference with (ops._cnf_route): the 128-point f16x3
+    kernel when it takes n points and the switch is on (the packs then come as _SolvePacks), the 64-point bf16x6 kernel otherwise
+    -> (f16x3?, w1, w2)."""
     if isinstance(w1x, _SolvePacks):
-        if n >= 128 and ops.cnf_tape_split() == "f16x3":
+        if ops._cnf_route(n, True, True) == "h3" and ops.cnf_tape_split() == "f16x3":
             return True, w1x.h3, w2x.h3
         return False, w1x.x6, w2x.x6
     return False, w1x, w2x

@@ -171,57 +171,45 @@ def cnf_train_fwd(y, logp, e, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_e
     tcol as ops.cnf_rk4 takes them, w1x / w2x = ops.pack_cnf_x6, t_end a one-element DEVICE tensor.
     -> y_T (BT,n,3), logp_T (BT,n,1), stage inputs ys (steps,4,BT,n,3), stage outputs ka (steps,4,BT,n,3), knd (steps,4,BT,n,1)."""
     _chk_f32(y, logp, e, hyper, tcol, w0, b0, b1, b2, w3, b3, t_end)
-    if y.dim() != 3 or y.shape[2] != 3:
-        raise ValueError("cnf_train_fwd: y must be (BT,n,3), got %s" % (tuple(y.shape),))
-    BT, n, _ = y.shape
-    if tuple(e.shape) != (BT, n, 3) or tuple(logp.shape) != (BT, n, 1):
-        raise ValueError("cnf_train_fwd: e %s / logp %s do not match y %s" % (tuple(e.shape), tuple(logp.shape), tuple(y.shape)))
-    if hyper.dim() != 2 or hyper.shape[0] != BT or hyper.stride(1) != 1 or hyper.shape[1] < 2 * (3 * 512 + 3) or tcol.numel() < 2 * (3 * 512 + 3):
-        raise ValueError("cnf_train_fwd: hyper must be (BT, >= 3078) rows and tcol hold 3078 floats, got %s / %s" % (tuple(hyper.shape), tuple(tcol.shape)))
-    if tuple(w0.shape) != (512, 3) or tuple(w3.shape) != (3, 512) or b0.numel() != 512 or b1.numel() != 512 or b2.numel() != 512 or b3.numel() != 3:
-        raise ValueError("cnf_train_fwd: the kernel is built for the 3-512-512-512-3 ODE function")
-    if w1x is None or w2x is None or w1x.numel() != _lib.load().caspr_cnf_x6_packed_bytes() or w2x.numel() != w1x.numel():
-        raise ValueError("cnf_train_fwd: the bf16x6 weight packs w1x / w2x (ops.pack_cnf_x6) are required")
-    if t_end.numel() != 1 or not t_end.is_cuda or steps <= 0:
-        raise ValueError("cnf_train_fwd: t_end must be a one-element device tensor and steps positive")
+    BT, n = ops._chk_cnf("cnf_train_fwd", y, hyper, e, logp, train=(tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_end), steps=steps)
     dev = y.device
     out = torch.empty(BT, n, 3, device=dev, dtype=torch.float32)
     lp_out = torch.empty(BT, n, 1, device=dev, dtype=torch.float32)
     ys = torch.empty(steps, 4, BT, n, 3, device=dev, dtype=torch.float32)
     ka = torch.empty(steps, 4, BT, n, 3, device=dev, dtype=torch.float32)
     knd = torch.empty(steps, 4, BT, n, 1, device=dev, dtype=torch.float32)
-    with ops.timed("cnf_train_fwd"):
-        _lib.check(_lib.load().caspr_cnf_train_fwd_f32(_p(y), _p(hyper), hyper.stride(0), _p(tcol), _p(w0), _p(b0), _p(w1x), _p(b1), _p(w2x), _p(b2),
-                                                       _p(w3), _p(b3), 512, _p(t_end), int(steps), _p(e), _p(logp), _p(lp_out), _p(out), _p(ys), _p(ka),
-                                                       _p(knd), BT, n, _stream()), "caspr_cnf_train_fwd_f32")
+    ops._cnf_launch("x6", "train_fwd", "cnf_train_fwd", dev, ops._cnf_head(y, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3),
+                    (_p(t_end), int(steps)), (_p(e), _p(logp), _p(lp_out), _p(out), _p(ys), _p(ka), _p(knd), BT, n))
     return out, lp_out, ys, ka, knd
+
+
+def _cnf_sample_tape(who, route, y, hyper, tcol, w0, b0, w1, b1, w2, b2, w3, b3, t_end, steps, table=None):
+    """The four sampling solves with a tape: `route` "x6" | "h3" with its packs w1 / w2; steps an int, or with table = (max_steps, order,
+    ys, ka) a step count per frame -> x_0, ys, ka."""
+    _chk_f32(y, hyper, tcol, w0, b0, b1, b2, w3, b3, t_end, *(table or ())[2:])
+    BT, n = ops._chk_cnf(who, y, hyper, train=(tcol, w0, b0, w1, b1, w2, b2, w3, b3, t_end), route=route,
+                         steps=steps if table is None and route == "x6" else None)
+    dev = y.device
+    if table is not None:
+        max_steps, ys, ka = ops._cnf_step_table(who, y, steps, table[1], table[0], table[2:])
+        step_args = (_p(steps), max_steps, _p(table[1]))
+    else:
+        if steps <= 0:                                   # (the bf16x6 wrapper has said so with t_end's message)
+            raise ValueError("%s: steps must be positive" % who)
+        ys = torch.empty(steps, 4, BT, n, 3, device=dev, dtype=torch.float32)
+        ka = torch.empty(steps, 4, BT, n, 3, device=dev, dtype=torch.float32)
+        step_args = (int(steps),)
+    out = torch.empty(BT, n, 3, device=dev, dtype=torch.float32)
+    ops._cnf_launch(route, "tape" if table is None else "tape_frames", "cnf_sample_tape", dev,
+                    ops._cnf_head(y, hyper, tcol, w0, b0, w1, b1, w2, b2, w3, b3), (_p(t_end), *step_args), (_p(out), _p(ys), _p(ka), BT, n))
+    return out, ys, ka
 
 
 def cnf_sample_tape(y, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_end, steps):
     """Sampling solve of one CNF block with its tape in one launch (caspr_cnf_sample_tape_f32): RK4 from t_end down to 0, no divergence.
     y (BT,n,3), hyper (BT, >= 3078) and tcol as ops.cnf_rk4 takes them, w1x / w2x = ops.pack_cnf_x6, t_end a one-element DEVICE tensor.
     -> x_0 (BT,n,3), stage inputs ys (steps,4,BT,n,3), stage outputs ka (steps,4,BT,n,3)."""
-    _chk_f32(y, hyper, tcol, w0, b0, b1, b2, w3, b3, t_end)
-    if y.dim() != 3 or y.shape[2] != 3:
-        raise ValueError("cnf_sample_tape: y must be (BT,n,3), got %s" % (tuple(y.shape),))
-    BT, n, _ = y.shape
-    if hyper.dim() != 2 or hyper.shape[0] != BT or hyper.stride(1) != 1 or hyper.shape[1] < 2 * (3 * 512 + 3) or tcol.numel() < 2 * (3 * 512 + 3):
-        raise ValueError("cnf_sample_tape: hyper must be (BT, >= 3078) rows and tcol hold 3078 floats, got %s / %s" % (tuple(hyper.shape), tuple(tcol.shape)))
-    if tuple(w0.shape) != (512, 3) or tuple(w3.shape) != (3, 512) or b0.numel() != 512 or b1.numel() != 512 or b2.numel() != 512 or b3.numel() != 3:
-        raise ValueError("cnf_sample_tape: the kernel is built for the 3-512-512-512-3 ODE function")
-    if w1x is None or w2x is None or w1x.numel() != _lib.load().caspr_cnf_x6_packed_bytes() or w2x.numel() != w1x.numel():
-        raise ValueError("cnf_sample_tape: the bf16x6 weight packs w1x / w2x (ops.pack_cnf_x6) are required")
-    if t_end.numel() != 1 or not t_end.is_cuda or steps <= 0:
-        raise ValueError("cnf_sample_tape: t_end must be a one-element device tensor and steps positive")
-    dev = y.device
-    out = torch.empty(BT, n, 3, device=dev, dtype=torch.float32)
-    ys = torch.empty(steps, 4, BT, n, 3, device=dev, dtype=torch.float32)
-    ka = torch.empty(steps, 4, BT, n, 3, device=dev, dtype=torch.float32)
-    with ops.timed("cnf_sample_tape"):
-        _lib.check(_lib.load().caspr_cnf_sample_tape_f32(_p(y), _p(hyper), hyper.stride(0), _p(tcol), _p(w0), _p(b0), _p(w1x), _p(b1), _p(w2x), _p(b2),
-                                                         _p(w3), _p(b3), 512, _p(t_end), int(steps), _p(out), _p(ys), _p(ka), BT, n, _stream()),
-                   "caspr_cnf_sample_tape_f32")
-    return out, ys, ka
+    return _cnf_sample_tape("cnf_sample_tape", "x6", y, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_end, steps)
 
 
 def cnf_sample_tape_frames(y, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_end, steps, max_steps, order=None, ys=None, ka=None):
@@ -231,56 +219,8 @@ def cnf_sample_tape_frames(y, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_e
     position p of the frame axis holds frame order[p] (p itself without an order), rows s < S_f only -- the rest of ys / ka is left
     as it was.  ys / ka (max_steps,4,BT,n,3) may be handed in (a test poisons them); allocated with torch.empty otherwise.
     -> x_0 (BT,n,3), ys, ka."""
-    _chk_f32(y, hyper, tcol, w0, b0, b1, b2, w3, b3, t_end, ys, ka)
-    if y.dim() != 3 or y.shape[2] != 3:
-        raise ValueError("cnf_sample_tape_frames: y must be (BT,n,3), got %s" % (tuple(y.shape),))
-    BT, n, _ = y.shape
-    if hyper.dim() != 2 or hyper.shape[0] != BT or hyper.stride(1) != 1 or hyper.shape[1] < 2 * (3 * 512 + 3) or tcol.numel() < 2 * (3 * 512 + 3):
-        raise ValueError("cnf_sample_tape_frames: hyper must be (BT, >= 3078) rows and tcol hold 3078 floats, got %s / %s" % (tuple(hyper.shape), tuple(tcol.shape)))
-    if tuple(w0.shape) != (512, 3) or tuple(w3.shape) != (3, 512) or b0.numel() != 512 or b1.numel() != 512 or b2.numel() != 512 or b3.numel() != 3:
-        raise ValueError("cnf_sample_tape_frames: the kernel is built for the 3-512-512-512-3 ODE function")
-    if w1x is None or w2x is None or w1x.numel() != _lib.load().caspr_cnf_x6_packed_bytes() or w2x.numel() != w1x.numel():
-        raise ValueError("cnf_sample_tape_frames: the bf16x6 weight packs w1x / w2x (ops.pack_cnf_x6) are required")
-    if t_end.numel() != 1 or not t_end.is_cuda:
-        raise ValueError("cnf_sample_tape_frames: t_end must be a one-element device tensor")
-    ops._chk_frame_table("steps", steps, BT, y.device)
-    if order is not None:
-        ops._chk_frame_table("order", order, BT, y.device)
-    max_steps = int(max_steps)
-    if not 1 <= max_steps <= ops.CNF_MAX_TABLE_STEPS:
-        raise ValueError("cnf_sample_tape_frames: max_steps must lie in 1..%d, got %d" % (ops.CNF_MAX_TABLE_STEPS, max_steps))
-    dev = y.device
-    shape = (max_steps, 4, BT, n, 3)           # max_steps is the kernel's clamp AND the tape's step rows: they must be the same number
-    for name, t in (("ys", ys), ("ka", ka)):
-        if t is not None and (tuple(t.shape) != shape or t.device != dev or not t.is_contiguous()):
-            raise ValueError("cnf_sample_tape_frames: %s must be a contiguous %s tensor on %s, got %s on %s" % (name, shape, dev, tuple(t.shape), t.device))
-    out = torch.empty(BT, n, 3, device=dev, dtype=torch.float32)
-    ys = torch.empty(shape, device=dev, dtype=torch.float32) if ys is None else ys
-    ka = torch.empty(shape, device=dev, dtype=torch.float32) if ka is None else ka
-    with ops.timed("cnf_sample_tape"):
-        _lib.check(_lib.load().caspr_cnf_sample_tape_frames_f32(_p(y), _p(hyper), hyper.stride(0), _p(tcol), _p(w0), _p(b0), _p(w1x), _p(b1), _p(w2x), _p(b2),
-                                                                _p(w3), _p(b3), 512, _p(t_end), _p(steps), max_steps, _p(order), _p(out), _p(ys), _p(ka),
-                                                                BT, n, _stream()), "caspr_cnf_sample_tape_frames_f32")
-    return out, ys, ka
-
-
-def _chk_sample_tape_h3(name, y, hyper, tcol, w0, b0, w1h, b1, w2h, b2, w3, b3, t_end):
-    """The argument checks the two f16x3 tape wrappers share -> (BT, n)."""
-    if y.dim() != 3 or y.shape[2] != 3:
-        raise ValueError("%s: y must be (BT,n,3), got %s" % (name, tuple(y.shape)))
-    BT, n, _ = y.shape
-    if n < 128:
-        raise ValueError("%s: n = %d is below the 128-point workgroup of the f16x3 kernel: %s is the wrapper for it" % (name, n, name.replace("_h3", "")))
-    if hyper.dim() != 2 or hyper.shape[0] != BT or hyper.stride(1) != 1 or hyper.shape[1] < 2 * (3 * 512 + 3) or tcol.numel() < 2 * (3 * 512 + 3):
-        raise ValueError("%s: hyper must be (BT, >= 3078) rows and tcol hold 3078 floats, got %s / %s" % (name, tuple(hyper.shape), tuple(tcol.shape)))
-    if tuple(w0.shape) != (512, 3) or tuple(w3.shape) != (3, 512) or b0.numel() != 512 or b1.numel() != 512 or b2.numel() != 512 or b3.numel() != 3:
-        raise ValueError("%s: the kernel is built for the 3-512-512-512-3 ODE function" % name)
-    nbytes = _lib.load().caspr_cnf_h3_packed_bytes()
-    if w1h is None or w2h is None or w1h.numel() != nbytes or w2h.numel() != nbytes or w1h.dtype != torch.uint8 or w2h.dtype != torch.uint8:
-        raise ValueError("%s: the f16x3 weight packs w1h / w2h (ops.pack_cnf_h3) are required" % name)
-    if t_end.numel() != 1 or not t_end.is_cuda:
-        raise ValueError("%s: t_end must be a one-element device tensor" % name)
-    return BT, n
+    return _cnf_sample_tape("cnf_sample_tape_frames", "x6", y, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_end, steps,
+                            (max_steps, order, ys, ka))
 
 
 def cnf_sample_tape_h3(y, hyper, tcol, w0, b0, w1h, b1, w2h, b2, w3, b3, t_end, steps):
@@ -289,53 +229,15 @@ def cnf_sample_tape_h3(y, hyper, tcol, w0, b0, w1h, b1, w2h, b2, w3, b3, t_end, 
     ops.cnf_rk4(..., w1h=, w2h=, reverse=True) returns for the same inputs, the same float32 t_end and the same steps.  The range guard
     (a point with a hidden activation of 4095 or more gets NaN in x_0) reports through ops.check_deferred_errors, as ops.cnf_rk4's.
     -> x_0 (BT,n,3), stage inputs ys (steps,4,BT,n,3), stage outputs ka (steps,4,BT,n,3)."""
-    _chk_f32(y, hyper, tcol, w0, b0, b1, b2, w3, b3, t_end)
-    BT, n = _chk_sample_tape_h3("cnf_sample_tape_h3", y, hyper, tcol, w0, b0, w1h, b1, w2h, b2, w3, b3, t_end)
-    if steps <= 0:
-        raise ValueError("cnf_sample_tape_h3: steps must be positive")
-    dev = y.device
-    out = torch.empty(BT, n, 3, device=dev, dtype=torch.float32)
-    ys = torch.empty(steps, 4, BT, n, 3, device=dev, dtype=torch.float32)
-    ka = torch.empty(steps, 4, BT, n, 3, device=dev, dtype=torch.float32)
-    with ops._cnf_h3.on(dev) as status:
-        word = status.word
-        with ops.timed("cnf_sample_tape"):
-            _lib.check(_lib.load().caspr_cnf_sample_tape_h3_f32(_p(y), _p(hyper), hyper.stride(0), _p(tcol), _p(w0), _p(b0), _p(w1h), _p(b1), _p(w2h),
-                                                                _p(b2), _p(w3), _p(b3), 512, _p(t_end), int(steps), _p(word), _p(out), _p(ys), _p(ka),
-                                                                BT, n, _stream()), "caspr_cnf_sample_tape_h3_f32")
-        status.post(word)
-    return out, ys, ka
+    return _cnf_sample_tape("cnf_sample_tape_h3", "h3", y, hyper, tcol, w0, b0, w1h, b1, w2h, b2, w3, b3, t_end, steps)
 
 
 def cnf_sample_tape_h3_frames(y, hyper, tcol, w0, b0, w1h, b1, w2h, b2, w3, b3, t_end, steps, max_steps, order=None, ys=None, ka=None):
     """cnf_sample_tape_frames on the 128-point f16x3 evaluation (caspr_cnf_sample_tape_h3_frames_f32; the kernel of cnf_sample_tape_h3):
     same arguments with w1h / w2h = ops.pack_cnf_h3, n >= 128; the tape in LAUNCH order, rows s < S_f only, ys / ka may be handed in.
     Frame f's x_0 is bit for bit what cnf_sample_tape_h3 gives on that frame alone with S_f steps.  -> x_0 (BT,n,3), ys, ka."""
-    _chk_f32(y, hyper, tcol, w0, b0, b1, b2, w3, b3, t_end, ys, ka)
-    BT, n = _chk_sample_tape_h3("cnf_sample_tape_h3_frames", y, hyper, tcol, w0, b0, w1h, b1, w2h, b2, w3, b3, t_end)
-    ops._chk_frame_table("steps", steps, BT, y.device)
-    if order is not None:
-        ops._chk_frame_table("order", order, BT, y.device)
-    max_steps = int(max_steps)
-    if not 1 <= max_steps <= ops.CNF_MAX_TABLE_STEPS:
-        raise ValueError("cnf_sample_tape_h3_frames: max_steps must lie in 1..%d, got %d" % (ops.CNF_MAX_TABLE_STEPS, max_steps))
-    dev = y.device
-    shape = (max_steps, 4, BT, n, 3)           # max_steps is the kernel's clamp AND the tape's step rows: they must be the same number
-    for name, t in (("ys", ys), ("ka", ka)):
-        if t is not None and (tuple(t.shape) != shape or t.device != dev or not t.is_contiguous()):
-            raise ValueError("cnf_sample_tape_h3_frames: %s must be a contiguous %s tensor on %s, got %s on %s" % (name, shape, dev, tuple(t.shape), t.device))
-    out = torch.empty(BT, n, 3, device=dev, dtype=torch.float32)
-    ys = torch.empty(shape, device=dev, dtype=torch.float32) if ys is None else ys
-    ka = torch.empty(shape, device=dev, dtype=torch.float32) if ka is None else ka
-    with ops._cnf_h3.on(dev) as status:
-        word = status.word
-        with ops.timed("cnf_sample_tape"):
-            _lib.check(_lib.load().caspr_cnf_sample_tape_h3_frames_f32(_p(y), _p(hyper), hyper.stride(0), _p(tcol), _p(w0), _p(b0), _p(w1h), _p(b1),
-                                                                       _p(w2h), _p(b2), _p(w3), _p(b3), 512, _p(t_end), _p(steps), max_steps, _p(order),
-                                                                       _p(word), _p(out), _p(ys), _p(ka), BT, n, _stream()),
-                       "caspr_cnf_sample_tape_h3_frames_f32")
-        status.post(word)
-    return out, ys, ka
+    return _cnf_sample_tape("cnf_sample_tape_h3_frames", "h3", y, hyper, tcol, w0, b0, w1h, b1, w2h, b2, w3, b3, t_end, steps,
+                            (max_steps, order, ys, ka))
 
 
 # ---- the gated softplus layers on value rows only (csrc/backward_flow_value.hip): R = frames * n rows, point p in row p.
