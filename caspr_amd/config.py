@@ -43,6 +43,8 @@ class KernelConfig:
                                         # (63 GB -> ~1/8 of tape at the cfg-3 shard for one more forward of the block)
     train_cnf_block_node: bool = False  # training: a CNF block as ONE autograd node (train/flow_grad.py: CnfBlockSolve): the forward in one launch
                                         # that writes no layer product (csrc/ode_train_fwd.hip), the reverse sweep taping one evaluation at a time
+    train_cnf_block_node_reg: bool = False  # training: the block node also carries the kinetic / Jacobian regularisers (CnfBlockSolveReg; needs
+                                        # train_cnf_block_node): cnf_block_train(reg=True) then runs on the node instead of refusing
 
 
 # environment name -> (field, parser); read only under CASPR_DEBUG=1
@@ -68,6 +70,7 @@ _ENV = {
     "CASPR_LATENT_NODE": ("train_latent_node", lambda v: v != "0"),
     "CASPR_CNF_CHECKPOINT": ("train_cnf_checkpoint", lambda v: v != "0"),
     "CASPR_CNF_BLOCK_NODE": ("train_cnf_block_node", lambda v: v != "0"),
+    "CASPR_CNF_BLOCK_NODE_REG": ("train_cnf_block_node_reg", lambda v: v != "0"),
 }
 
 

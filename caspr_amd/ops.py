@@ -1223,7 +1223,8 @@ CNF_H3_POINTS = 128                       # the f16x3 workgroup's point count
 _CNF_ENTRY = {
     "f32": {"rk4": "caspr_cnf_rk4_f32"},
     "x6": {"rk4": "caspr_cnf_rk4_x6_f32", "frames": "caspr_cnf_rk4_x6_frames_f32", "dopri5": "caspr_cnf_dopri5_f32",
-           "train_fwd": "caspr_cnf_train_fwd_f32", "tape": "caspr_cnf_sample_tape_f32", "tape_frames": "caspr_cnf_sample_tape_frames_f32"},
+           "train_fwd": "caspr_cnf_train_fwd_f32", "train_fwd_reg": "caspr_cnf_block_reg_fwd_f32", "tape": "caspr_cnf_sample_tape_f32",
+           "tape_frames": "caspr_cnf_sample_tape_frames_f32"},
     "h3": {"rk4": "caspr_cnf_rk4_h3_f32", "frames": "caspr_cnf_rk4_h3_frames_f32", "dopri5": "caspr_cnf_dopri5_h3_f32",
            "tape": "caspr_cnf_sample_tape_h3_f32", "tape_frames": "caspr_cnf_sample_tape_h3_frames_f32"},
 }

@@ -22,6 +22,7 @@ step count per frame (decode(differentiable=True, frame_steps=...)).
 The three block nodes -- CnfBlockSolve (forward direction, value + divergence), CnfSampleSolve, CnfSampleSolveFrames -- each launch one
 taping solve kernel forward and share ONE hand-written reverse sweep, _rk4_reverse_sweep, whose docstring states the RK4 algebra; a
 node's backward only describes its variant (outputs, time axis, scalar or per frame) and forms dL/dt_end from what the sweep returns.
+CnfBlockSolveReg is CnfBlockSolve with the kinetic / Jacobian regularisers as a third, summed output (config.train_cnf_block_node_reg).
 """
 import collections
 import functools
@@ -661,6 +662,7 @@ HIDDEN_NODE = _cfg.train_cnf_hidden_node    # False: CnfLayer + CnfLayerOut
 LATENT_NODE = _cfg.train_latent_node        # False: the per-layer form
 CHECKPOINT_STEPS = _cfg.train_cnf_checkpoint   # True: the CNF's tape per RK4 step, recomputed in the backward pass (cnf_block_train)
 BLOCK_NODE = _cfg.train_cnf_block_node      # True: a CNF block as one autograd node (CnfBlockSolve) where the shape allows; wins over CHECKPOINT_STEPS
+BLOCK_NODE_REG = _cfg.train_cnf_block_node_reg   # True (with BLOCK_NODE): cnf_block_train(reg=True) on the node too (CnfBlockSolveReg) instead of refusing
 
 
 def latent_solve_train(lat, z0, times):
@@ -698,6 +700,16 @@ def _cnf_eval_fused(wb, t, y, G_lm, Bb_lm, tg_lm, tb_lm, e_rows, BT, n, widths):
     h = CnfIn.apply(y.reshape(BT * n, 3), e_rows, w0, b0, parts[0], parts[4], n, 32)
     z = CnfHidden.apply(h, w1, b1, parts[1], parts[5], w2, b2, parts[2], parts[6], w3, n)
     return CnfOut.apply(z, b3, parts[3], parts[7], e_rows, n, 32)
+
+
+def _cnf_eval_fused_reg(wb, t, y, G_lm, Bb_lm, tg_lm, tb_lm, e_rows, BT, n, widths):
+    """_cnf_eval_fused with CnfOutReg at its end: the same nodes up to the output product -> a (BT,n,3), nd (BT,n,1) [its bits] and
+    q (BT,n,2) = (|a|^2, |J e|^2), the regularisers' integrands.  What CnfBlockSolveReg's reverse sweep rebuilds and differentiates."""
+    w0, b0, w1, b1, w2, b2, w3, b3 = wb
+    parts = SplitLayers.apply(torch.sigmoid(G_lm + t * tg_lm), Bb_lm + t * tb_lm, BT, widths)
+    h = CnfIn.apply(y.reshape(BT * n, 3), e_rows, w0, b0, parts[0], parts[4], n, 32)
+    z = CnfHidden.apply(h, w1, b1, parts[1], parts[5], w2, b2, parts[2], parts[6], w3, n)
+    return CnfOutReg.apply(z, b3, parts[3], parts[7], e_rows, n, 32)
 
 
 def _hyper_layer_major(block, context):
@@ -895,30 +907,77 @@ class CnfBlockSolve(torch.autograd.Function):
         return (gy, glp, d_hyp[0], d_hyp[1], d_hyp[2], d_hyp[3], dt_end, None, None, None, None, None) + tuple(d_wb)
 
 
+class CnfBlockSolveReg(torch.autograd.Function):
+    """CnfBlockSolve with the kinetic and Jacobian regularisers (Finlay et al. 2020) as a third output: forward = one launch of
+    caspr_cnf_block_reg_fwd_f32, the same kernel's REG instantiation, which also integrates r' = (|a|^2, |J e|^2) from r(0) = 0 and tapes
+    every evaluation's integrands kq (S,4,BT,n,2); x_T, logp_T and the tape ys / ka / knd are CnfBlockSolve's bits.  Backward =
+    _rk4_reverse_sweep with the third tape kq and r_T's cotangent beside logp_T's (r_{s+1} = r_s + ...: the same at every step, as
+    logp's), the evaluation _cnf_eval_fused_reg (CnfOutReg at its end); dL/dt_end = (dL/dh) / S then holds <gr, sum_i w_i q_i> through
+    the sweep's dot over the output tapes.  With r_T left out of the loss (autograd hands None for its cotangent: the node does not
+    have it materialised) the backward is CnfBlockSolve's, call for call -- CnfOut, two tapes -- and so are the gradients' bits.
+    Arguments as CnfBlockSolve's -> (x_T, logp_T, r_T (BT,n,2))."""
+
+    @staticmethod
+    def forward(ctx, x, logpx, G_lm, Bb_lm, tg_lm, tb_lm, t_end, e, w1x, w2x, steps, widths, *wb):
+        BT, n, _ = x.shape
+        hyper, tcol = _hyper_for_kernel(G_lm, Bb_lm, tg_lm, tb_lm, BT, widths)
+        w0, b0, w1, b1, w2, b2, w3, b3 = [t_.detach().contiguous() for t_ in wb]
+        ec = e.detach().contiguous()
+        y, lp, r, ys, ka, knd, kq = T.cnf_block_reg_fwd(x.detach().contiguous(), logpx.detach().contiguous(), ec, hyper, tcol, w0, b0, w1x, b1, w2x, b2,
+                                                        w3, b3, t_end.detach().reshape(1).contiguous(), steps)
+        ctx.save_for_backward(ys, ka, knd, kq, G_lm, Bb_lm, tg_lm, tb_lm, t_end, ec)
+        ctx.steps, ctx.widths, ctx.wb = steps, widths, wb
+        ctx.set_materialize_grads(False)               # a None for r_T's cotangent says that r is not in the loss
+        return y, lp, r
+
+    @staticmethod
+    def backward(ctx, gy, glp, gr):
+        ys, ka, knd, kq, G_lm, Bb_lm, tg_lm, tb_lm, t_end, e = ctx.saved_tensors
+        S, widths, wb = ctx.steps, ctx.widths, ctx.wb
+        _, _, BT, n, _ = ys.shape
+        gy = torch.zeros(BT, n, 3, device=ys.device, dtype=ys.dtype) if gy is None else gy.contiguous()
+        glp = torch.zeros(BT, n, 1, device=ys.device, dtype=ys.dtype) if glp is None else glp.contiguous()
+        h = (t_end.detach() / S).reshape(())
+        e_rows = e.reshape(BT * n, 3)
+        if gr is None:                                   # CnfBlockSolve.backward's computation
+            tapes, g_rest = (ka, knd), (glp,)
+            evaluate = lambda t, y_in, hyp, F: _cnf_eval_fused(wb, t, y_in, hyp[0], hyp[1], hyp[2], hyp[3], e_rows, F, n, widths)
+        else:
+            tapes, g_rest = (ka, knd, kq), (glp, gr.contiguous())
+            evaluate = lambda t, y_in, hyp, F: _cnf_eval_fused_reg(wb, t, y_in, hyp[0], hyp[1], hyp[2], hyp[3], e_rows, F, n, widths)
+        gy, d_hyp, d_wb, dh, _ = _rk4_reverse_sweep(ys, tapes, gy, g_rest, h, lambda s, c, h_: h_ * s + c * h_, False, evaluate,
+                                                    (G_lm, Bb_lm, tg_lm, tb_lm), wb, widths)
+        dt_end = (dh / S).to(t_end.dtype).reshape(t_end.shape)
+        return (gy, glp, d_hyp[0], d_hyp[1], d_hyp[2], d_hyp[3], dt_end, None, None, None, None, None) + tuple(d_wb)
+
+
 def cnf_block_train(block, x, context, logpx, e, reg=False):
     """x (BT,n,3), context (BT,zdim), logpx (BT,n,1), e (BT,n,3) fixed Hutchinson noise.  Forward direction
     t: 0 -> sqrt_end_time^2 with `block.rk4_steps` RK4 steps.  -> (x_T, logp_T), differentiable in every parameter.
     reg=True (opt-in; Finlay et al. 2020): the ODE state gains r (BT,n,2), r(0) = 0, r' = (|f|^2, |J e|^2) -- the kinetic energy and
     the Hutchinson estimate of |df/dy|_F^2 along every trajectory, integrated by the same RK4 weights as logp -> (x_T, logp_T, r_T);
     x_T and logp_T are the bits of reg=False.  J e is what the tangent rows carry (forward mode), so the Jacobian term is |J e|^2, not
-    RNODE's |e^T J|^2; both have expectation |J|_F^2 for e ~ N(0, I).  Taped and checkpointed routes only: the block node's one-launch
-    forward does not write J e, and reg=True with config.train_cnf_block_node raises -- whenever the switch is on, also for a shape the
-    node would not take (n no multiple of 64, no bf16x6): the answer does not depend on the batch; turn the switch off to regularise."""
+    RNODE's |e^T J|^2; both have expectation |J|_F^2 for e ~ N(0, I).  On the taped and checkpointed routes, and on the block node with
+    config.train_cnf_block_node_reg (opt-in; CnfBlockSolveReg, where CnfBlockSolve would take the shape; the taped reg=True route
+    otherwise).  With config.train_cnf_block_node alone reg=True raises: the plain node's forward does not write J e -- whenever that
+    switch is on, also for a shape the node would not take (n no multiple of 64, no bf16x6): the answer does not depend on the batch."""
     layers = block.odefunc.diffeq.layers
     BT, n, _ = x.shape
-    if reg and BLOCK_NODE:
+    if reg and BLOCK_NODE and not BLOCK_NODE_REG:
         raise ValueError("cnf_block_train(reg=True) does not run on the block node (config.train_cnf_block_node): its one-launch forward "
                          "does not write J e, which the Jacobian regulariser integrates; turn that switch off (it refuses for every shape, "
-                         "also one the node would not take); config.train_cnf_checkpoint is the low-memory route that carries the regularisers")
+                         "also one the node would not take); config.train_cnf_checkpoint is the low-memory route that carries the regularisers.  "
+                         "config.train_cnf_block_node_reg, turned on beside it, runs the node that does integrate them (CnfBlockSolveReg)")
     fused = all(_fused_layer_ok(l, n) for l in layers[1:3])
     # BLOCK_NODE (config.train_cnf_block_node; off by default): the whole solve as one node with a tape of (BT,n,3) tensors only
-    # (CnfBlockSolve), where the fused-layer kernels and the bf16x6 CNF kernel apply; `_block_node_used` tells tests / tools which route ran
+    # (CnfBlockSolve; reg=True under BLOCK_NODE_REG: CnfBlockSolveReg), where the fused-layer kernels and the bf16x6 CNF kernel apply;
+    # `_block_node_used` tells tests / tools which route ran
     block._block_node_used = bool(BLOCK_NODE and fused and ops.CNF_BF16X6 and tuple(l._layer.weight.shape[0] for l in layers) == (512, 512, 512, 3))
     if block._block_node_used:
         (G_lm, Bb_lm, tg_lm, tb_lm, widths), t_end, w1x, w2x, wb = _block_node_inputs(block, context, x.device)
-        y, lp = CnfBlockSolve.apply(x, logpx, G_lm, Bb_lm, tg_lm, tb_lm, t_end, e, w1x, w2x, block.rk4_steps, widths, *wb)
+        out = (CnfBlockSolveReg if reg else CnfBlockSolve).apply(x, logpx, G_lm, Bb_lm, tg_lm, tb_lm, t_end, e, w1x, w2x, block.rk4_steps, widths, *wb)
         block.odefunc._num_evals.fill_(4 * block.rk4_steps)
-        return y, lp
+        return out
     # hyper networks: the context columns once per solve, the time column per evaluation; layer-major 1-D tensors (_hyper_layer_major)
     G_lm, Bb_lm, tg_lm, tb_lm, widths = _hyper_layer_major(block, context)
     e_rows = e.reshape(BT * n, 3)

@@ -183,6 +183,25 @@ def cnf_train_fwd(y, logp, e, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_e
     return out, lp_out, ys, ka, knd
 
 
+def cnf_block_reg_fwd(y, logp, e, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_end, steps):
+    """cnf_train_fwd with the kinetic / Jacobian regularisers integrated beside the log-density (caspr_cnf_block_reg_fwd_f32, the same
+    kernel's REG instantiation): same arguments -> y_T (BT,n,3), logp_T (BT,n,1), r_T (BT,n,2) = the integrals of (|dy/dt|^2, |J e|^2),
+    ys, ka, knd as there -- those five the bits of cnf_train_fwd -- and every evaluation's integrands kq (steps,4,BT,n,2)."""
+    _chk_f32(y, logp, e, hyper, tcol, w0, b0, b1, b2, w3, b3, t_end)
+    BT, n = ops._chk_cnf("cnf_block_reg_fwd", y, hyper, e, logp, train=(tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_end), steps=steps)
+    dev = y.device
+    out = torch.empty(BT, n, 3, device=dev, dtype=torch.float32)
+    lp_out = torch.empty(BT, n, 1, device=dev, dtype=torch.float32)
+    r_out = torch.empty(BT, n, 2, device=dev, dtype=torch.float32)
+    ys = torch.empty(steps, 4, BT, n, 3, device=dev, dtype=torch.float32)
+    ka = torch.empty(steps, 4, BT, n, 3, device=dev, dtype=torch.float32)
+    knd = torch.empty(steps, 4, BT, n, 1, device=dev, dtype=torch.float32)
+    kq = torch.empty(steps, 4, BT, n, 2, device=dev, dtype=torch.float32)
+    ops._cnf_launch("x6", "train_fwd_reg", "cnf_block_reg_fwd", dev, ops._cnf_head(y, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3),
+                    (_p(t_end), int(steps)), (_p(e), _p(logp), _p(lp_out), _p(out), _p(r_out), _p(ys), _p(ka), _p(knd), _p(kq), BT, n))
+    return out, lp_out, r_out, ys, ka, knd, kq
+
+
 def _cnf_sample_tape(who, route, y, hyper, tcol, w0, b0, w1, b1, w2, b2, w3, b3, t_end, steps, table=None):
     """The four sampling solves with a tape: `route` "x6" | "h3" with its packs w1 / w2; steps an int, or with table = (max_steps, order,
     ys, ka) a step count per frame -> x_0, ys, ka."""

@@ -247,6 +247,17 @@ int caspr_cnf_train_fwd_f32(const float *y_in, const float *hyper, int ldh, cons
                             int H, const float *t_end, int steps, const float *e, const float *logp_in, float *logp_out,
                             float *y_out, float *ys, float *ka, float *knd, int BT, int n, void *stream);
 
+/* The same launch with the kinetic and Jacobian regularisers of Finlay et al. 2020 integrated beside the log-density (the kernel's REG
+ * instantiation; train/flow_grad.py: CnfBlockSolveReg): r' = (|dy/dt|^2, |J e|^2), r(0) = 0, with the RK4 weights of logp; J e is what
+ * the tangent columns carry, so the Jacobian term is the forward-mode estimator, as caspr_cnf_out_reg_f32's.  Writes, besides
+ * everything caspr_cnf_train_fwd_f32 writes -- y_out, logp_out, ys, ka, knd are ITS bits for the same inputs --, r_out (BT,n,2) and every
+ * evaluation's integrands kq (steps,4,BT,n,2) = (|dy/dt|^2, |J e|^2); r_out and kq non-NULL.  Plain stores by the lane that owns the
+ * value, no atomics; the columns of a partial workgroup write nothing.  A frame's results do not depend on the batch around it.       */
+int caspr_cnf_block_reg_fwd_f32(const float *y_in, const float *hyper, int ldh, const float *tcol, const float *w0, const float *b0,
+                                const void *w1x, const float *b1, const void *w2x, const float *b2, const float *w3, const float *b3,
+                                int H, const float *t_end, int steps, const float *e, const float *logp_in, float *logp_out,
+                                float *y_out, float *r_out, float *ys, float *ka, float *knd, float *kq, int BT, int n, void *stream);
+
 /* The SAMPLING solve of one point-CNF block with the tape its gradient needs (csrc/ode_sample_tape.hip; train/flow_grad.py:
  * CnfSampleSolve) -- the reference's cnf.py:70-128 with reverse = True and logpx = None, which caspr.py:262 runs in decode() and
  * differentiates through torchdiffeq: `steps` classic RK4 steps from *t_end DOWN to 0 (h = -t_end / steps), no divergence, ONE launch,
