@@ -39,6 +39,8 @@ class KernelConfig:
     train_cnf_out_node: bool = True     # training: the ODE function's output epilogue as one node (train/flow_grad.py)
     train_cnf_hidden_node: bool = True  # training: the hidden layers with the activation backward in the data-gradient conv
     train_latent_node: bool = True      # training: the latent solve as one autograd node (team tape + team adjoint)
+    train_latent_dopri5: bool = False   # training: LatentODE(method="dopri5") under autograd runs the adaptive solve's node (train/flow_grad.py: LatentSolveDopri5,
+                                        # csrc/ode_latent_dp5_adjoint.inc) instead of refusing: the gradient of the solve's own steps, held fixed; opt-in
     train_cnf_checkpoint: bool = False  # training: keep the CNF's state per RK4 step only, recompute the step in the backward pass
                                         # (63 GB -> ~1/8 of tape at the cfg-3 shard for one more forward of the block)
     train_cnf_block_node: bool = False  # training: a CNF block as ONE autograd node (train/flow_grad.py: CnfBlockSolve): the forward in one launch
@@ -68,6 +70,7 @@ _ENV = {
     "CASPR_CNF_OUT_NODE": ("train_cnf_out_node", lambda v: v != "0"),
     "CASPR_CNF_NODE": ("train_cnf_hidden_node", lambda v: v != "0"),
     "CASPR_LATENT_NODE": ("train_latent_node", lambda v: v != "0"),
+    "CASPR_TRAIN_LATENT_DP5": ("train_latent_dopri5", lambda v: v != "0"),
     "CASPR_CNF_CHECKPOINT": ("train_cnf_checkpoint", lambda v: v != "0"),
     "CASPR_CNF_BLOCK_NODE": ("train_cnf_block_node", lambda v: v != "0"),
     "CASPR_CNF_BLOCK_NODE_REG": ("train_cnf_block_node_reg", lambda v: v != "0"),

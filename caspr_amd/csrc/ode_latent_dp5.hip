@@ -24,75 +24,31 @@
 // A sequence's output, trace and counters are bit-identical whichever column, workgroup or batch it sits in.
 // The controller's rules (next step, initial step, interpolant) are dp5_rules.h's and the tableau dp5_tables.inc's: one text with
 // the two point-CNF solves.
-#include <math.h>
-#include <stdlib.h>
-
-#include "common.h"
+#include "ode_latent_dp5.h"
 #include "dp5_rules.h"
-
-#define LDP_NCOL 16
-#define LDP_EL (64 * LDP_NCOL)    // one state array: [d][c]
-#define LDP_TRACE_HEAD 8          // floats per sequence before the attempt rows: d0, d1, d2, h0, first dt, 0, 0, 0
-#define LDP_TRACE_ROW 4           // per attempt: t, dt, ratio, accepted (1 / 0)
 
 // the tableau (dp5_tables.inc), in this file's constant memory as LDP_BETA, LDP_CERR, LDP_CMID (the dynamics do not read t: no stage times)
 #define DP5_TAB(x) LDP_##x
 #define DP5_TAB_NO_ALPHA
 #include "dp5_tables.inc"
 
-// out rows [16*rt0, 16*(rt0+nrt)) of W (packed, KC chunks) times the B-tile `in`; epilogue(rt, acc)   (lat_layer of ode.hip)
-template <int NRT, typename Epi>
-__device__ __forceinline__ void ldp_layer(const float *__restrict__ wp, int KC, int rt0, const float *in, int lane, Epi epi)
-{
-    // One CU streams the whole weight set from L2 every evaluation: keep 4 chunks (4 x NRT KiB per wave,
-    // 128 KiB per workgroup) of A fragments in flight in a register ring to cover the L2 latency.
-    const int g = lane >> 4, j = lane & 15;
-    f32x4 acc[NRT];
-#pragma unroll
-    for (int i = 0; i < NRT; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const float *wb = wp + ((long)rt0 * KC) * 256 + lane * 4;
-    f32x4 ring[4][NRT];
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int i = 0; i < NRT; ++i) ring[s][i] = ld4(wb + ((long)i * KC + (s < KC ? s : 0)) * 256);
-    for (int kc0 = 0; kc0 < KC; kc0 += 4) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int kc = kc0 + s;
-            if (kc < KC) {
-                const f32x4 bf = ld4(in + btile_off(kc * 4 + g, j, LDP_NCOL));
-#pragma unroll
-                for (int i = 0; i < NRT; ++i) {
-                    const f32x4 af = ring[s][i];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) acc[i] = mfma16(af[q], bf[q], acc[i]);
-                }
-                const int kn = (kc + 4 < KC) ? kc + 4 : kc;
-#pragma unroll
-                for (int i = 0; i < NRT; ++i) ring[s][i] = ld4(wb + ((long)i * KC + kn) * 256);
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < NRT; ++i) epi(rt0 + i, acc[i]);
-}
+// the hooks of ode_latent_dp5_eval.inc: the solve keeps y_new (row 7 of the stage inputs) and no layer rows
+#define LDP_EVAL_IN(row, i, d, c, v) if (row == 7) s_yn[i] = v;
+#define LDP_EVAL_ROW(l, r, v)
 
-// sum over the 64 lanes in one fixed order; every lane returns the same bits (a + b == b + a)
-__device__ __forceinline__ double ldp_wave_sum(double v)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
+// TAPE: the solve under autograd (caspr_latent_dopri5_tape_f32).  The same text and the same bits in out / trace / counters; every
+// accepted step n of a sequence also leaves its start state z_n in tape_z (B, max_steps, D) and its size in tape_dt (B, max_steps),
+// which is all the reverse sweep (ode_latent_dp5_adjoint.inc) needs to rebuild the step.  A sequence whose next accepted step would
+// not fit stops like one that used up max_attempts: finished = 0, NaN in the rows it did not reach; that attempt is not counted.
+template <bool TAPE>
 __global__ __launch_bounds__(512) void latent_dp5_kernel(const float *__restrict__ z0, int ldz, const float *__restrict__ times,
                                                          int B, int Tu, int D, int H, float rtol, float atol, int max_attempts,
                                                          const float *__restrict__ w0p, const float *__restrict__ b0,
                                                          const float *__restrict__ w1p, const float *__restrict__ b1,
                                                          const float *__restrict__ w2p, const float *__restrict__ b2,
                                                          const float *__restrict__ w3p, const float *__restrict__ b3,
-                                                         float *__restrict__ out, float *__restrict__ trace, int *__restrict__ counters)
+                                                         float *__restrict__ out, float *__restrict__ trace, int *__restrict__ counters,
+                                                         float *__restrict__ tape_z, float *__restrict__ tape_dt, int max_steps)
 {
     // B-tiles: stage input (64 x 16, padded to 32 k-rows of 4), two hidden buffers (512 x 16)
     __shared__ __attribute__((aligned(16))) float s_in[16 * LDP_NCOL * 4];
@@ -118,62 +74,7 @@ __global__ __launch_bounds__(512) void latent_dp5_kernel(const float *__restrict
     if (tid < LDP_NCOL) { s_dt[tid] = 0.f; s_done[tid] = b0i + tid < B ? 0 : 1; }
     __syncthreads();
 
-    // s_in = z + dt_c * sum_q LDP_BETA[row][q] k_{q+1} as a B-tile (row d, col c); row 7 is y_new: kept
-    auto write_in = [&](int row) {
-        for (int i = tid; i < LDP_EL; i += 512) {
-            const int d = i / LDP_NCOL, c = i % LDP_NCOL;
-            if (d < D) {
-                float acc = 0.f;
-                for (int q = 0; q + 2 <= row && q < 6; ++q) {
-                    const float bq = LDP_BETA[row][q];
-                    if (bq != 0.f) acc += bq * s_k[q][i];
-                }
-                if (row == 1) acc = s_k[0][i];
-                const float v = s_z[i] + s_dt[c] * acc;
-                s_in[btile_off(d >> 2, c, LDP_NCOL) + (d & 3)] = v;
-                if (row == 7) s_yn[i] = v;
-            }
-        }
-    };
-    auto dyn = [&](float *kout) {  // s_in -> kout ; latent_ode_model.py:139-147 (Linear-Tanh x3, Linear)
-        __syncthreads();
-        for (int rt = wave * 4; rt < RTH; rt += 32)
-            ldp_layer<4>(w0p, KC0, rt, s_in, lane, [&](int r, f32x4 a) {
-                const f32x4 bb = ld4(b0 + r * 16 + 4 * g);
-                f32x4 v;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = tanhf(a[q] + bb[q]);
-                st4(s_h1 + btile_off(r * 4 + g, j, LDP_NCOL), v);
-            });
-        __syncthreads();
-        for (int rt = wave * 4; rt < RTH; rt += 32)
-            ldp_layer<4>(w1p, KCH, rt, s_h1, lane, [&](int r, f32x4 a) {
-                const f32x4 bb = ld4(b1 + r * 16 + 4 * g);
-                f32x4 v;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = tanhf(a[q] + bb[q]);
-                st4(s_h2 + btile_off(r * 4 + g, j, LDP_NCOL), v);
-            });
-        __syncthreads();
-        for (int rt = wave * 4; rt < RTH; rt += 32)
-            ldp_layer<4>(w2p, KCH, rt, s_h2, lane, [&](int r, f32x4 a) {
-                const f32x4 bb = ld4(b2 + r * 16 + 4 * g);
-                f32x4 v;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = tanhf(a[q] + bb[q]);
-                st4(s_h1 + btile_off(r * 4 + g, j, LDP_NCOL), v);
-            });
-        __syncthreads();
-        if (wave < RTD)
-            ldp_layer<1>(w3p, KCH, wave, s_h1, lane, [&](int r, f32x4 a) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int d = r * 16 + 4 * g + q;
-                    if (d < D) kout[d * LDP_NCOL + j] = a[q] + b3[d];
-                }
-            });
-        __syncthreads();
-    };
+#include "ode_latent_dp5_eval.inc"
 
     // ---- the control state of this wave's two columns (wave-uniform), lane = component d
     const bool dv = lane < D;
@@ -183,7 +84,7 @@ __global__ __launch_bounds__(512) void latent_dp5_kernel(const float *__restrict
     double tc[2] = {0.0, 0.0};                       // solver time, relative to times[0]
     float dtc[2] = {0.f, 0.f}, h0c[2] = {0.f, 0.f}, d0c[2] = {0.f, 0.f}, d1c[2] = {0.f, 0.f};
     int cur[2] = {0, 0}, nacc[2] = {0, 0}, nrej[2] = {0, 0};
-    bool fin[2], valid[2];
+    bool fin[2], valid[2], over[2] = {false, false};         // over: the tape is full (TAPE only)
 #pragma unroll
     for (int cc = 0; cc < 2; ++cc) { valid[cc] = b0i + 2 * wave + cc < B; fin[cc] = !valid[cc]; }
 
@@ -289,11 +190,22 @@ __global__ __launch_bounds__(512) void latent_dp5_kernel(const float *__restrict
             const float r = (float)(ldp_wave_sum(dv ? (double)qe * (double)qe : 0.0) / dD);     // mean((err / tol)^2)
             const bool accept = r <= 1.f;
             const float dt_next = dp5_next_dt(r, dt);
+            if constexpr (TAPE)
+                if (accept && nacc[cc] >= max_steps) {
+                    over[cc] = fin[cc] = true;
+                    if (lane == 0) { s_dt[c] = 0.f; s_done[c] = 1; }
+                    continue;
+                }
             if (trace && lane < LDP_TRACE_ROW) {
                 const float v = lane == 0 ? (float)tc[cc] : lane == 1 ? dt : lane == 2 ? r : (accept ? 1.f : 0.f);
                 trace[(long)(b0i + c) * (LDP_TRACE_HEAD + LDP_TRACE_ROW * max_attempts) + LDP_TRACE_HEAD + LDP_TRACE_ROW * att + lane] = v;
             }
             if (accept) {
+                if constexpr (TAPE) {
+                    float *tz = tape_z + ((long)(b0i + c) * max_steps + nacc[cc]) * D;
+                    if (dv) tz[lane] = z;
+                    if (lane == 0) tape_dt[(long)(b0i + c) * max_steps + nacc[cc]] = dt;
+                }
                 ++nacc[cc];
                 const double t0 = tc[cc], t1 = tc[cc] + (double)dt;
                 const float ymid = z + dt * ms;
@@ -314,7 +226,7 @@ __global__ __launch_bounds__(512) void latent_dp5_kernel(const float *__restrict
         if (!valid[cc]) continue;
         const long b = b0i + 2 * wave + cc;
         const int na = nacc[cc] + nrej[cc];
-        if (lane < 4) counters[b * 4 + lane] = lane == 0 ? nacc[cc] : lane == 1 ? nrej[cc] : lane == 2 ? 2 + 6 * na : (fin[cc] ? 1 : 0);
+        if (lane < 4) counters[b * 4 + lane] = lane == 0 ? nacc[cc] : lane == 1 ? nrej[cc] : lane == 2 ? 2 + 6 * na : (fin[cc] && !(TAPE && over[cc]) ? 1 : 0);
         if (dv)
             for (int i = cur[cc]; i < Tu; ++i) out[(b * Tu + i) * D + lane] = __builtin_nanf("");
         if (trace) {
@@ -338,9 +250,34 @@ extern "C" int caspr_latent_dopri5_f32(const float *z0, int ldz, const float *ti
         caspr_set_error("latent_dopri5: unsupported sizes D=%d H=%d (need D<=64, H<=512, H %% 64 == 0)", D, H);
         return CASPR_EUNSUP;
     }
-    latent_dp5_kernel<<<dim3(ceil_div(B, LDP_NCOL)), dim3(512), 0, (hipStream_t)stream>>>(z0, ldz, times, B, Tu, D, H, rtol, atol, max_attempts,
-                                                                                         w0p, b0, w1p, b1, w2p, b2, w3p, b3, out, trace,
-                                                                                         (int *)counters);
+    latent_dp5_kernel<false><<<dim3(ceil_div(B, LDP_NCOL)), dim3(512), 0, (hipStream_t)stream>>>(z0, ldz, times, B, Tu, D, H, rtol, atol, max_attempts,
+                                                                                                w0p, b0, w1p, b1, w2p, b2, w3p, b3, out, trace,
+                                                                                                (int *)counters, nullptr, nullptr, 0);
     CASPR_CHECK_LAUNCH("latent_dopri5");
     return CASPR_OK;
 }
+
+extern "C" int caspr_latent_dopri5_tape_f32(const float *z0, int ldz, const float *times, int B, int Tu, int D, int H,
+                                            float rtol, float atol, int max_attempts, int max_steps, const float *w0p, const float *b0,
+                                            const float *w1p, const float *b1, const float *w2p, const float *b2,
+                                            const float *w3p, const float *b3, float *out, float *trace, int32_t *counters,
+                                            float *tape_z, float *tape_dt, void *stream)
+{
+    CASPR_REQUIRE(z0 && times && out && counters && tape_z && tape_dt && w0p && w1p && w2p && w3p && b0 && b1 && b2 && b3,
+                  "latent_dopri5_tape: null pointer");
+    CASPR_REQUIRE(B > 0 && Tu > 0 && max_attempts > 0 && max_steps > 0 && D > 0 && H > 0 && ldz >= D,
+                  "latent_dopri5_tape: bad sizes B=%d Tu=%d D=%d H=%d ldz=%d max_attempts=%d max_steps=%d", B, Tu, D, H, ldz, max_attempts, max_steps);
+    CASPR_REQUIRE(rtol > 0.f && atol > 0.f && isfinite(rtol) && isfinite(atol), "latent_dopri5_tape: rtol and atol must be positive and finite");
+    if (!(D <= 64 && H <= 512 && H % 64 == 0)) {
+        caspr_set_error("latent_dopri5_tape: unsupported sizes D=%d H=%d (need D<=64, H<=512, H %% 64 == 0)", D, H);
+        return CASPR_EUNSUP;
+    }
+    latent_dp5_kernel<true><<<dim3(ceil_div(B, LDP_NCOL)), dim3(512), 0, (hipStream_t)stream>>>(z0, ldz, times, B, Tu, D, H, rtol, atol, max_attempts,
+                                                                                               w0p, b0, w1p, b1, w2p, b2, w3p, b3, out, trace,
+                                                                                               (int *)counters, tape_z, tape_dt, max_steps);
+    CASPR_CHECK_LAUNCH("latent_dopri5_tape");
+    return CASPR_OK;
+}
+
+// the reverse sweep of the taped solve: latent_dp5_adjoint_kernel, caspr_latent_dopri5_adjoint_f32
+#include "ode_latent_dp5_adjoint.inc"

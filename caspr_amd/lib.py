@@ -83,6 +83,10 @@ SIGNATURES = {
     "caspr_latent_rk4_f32": (c_int, [c_fp, c_int, c_fp, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_stream]),
     "caspr_latent_dopri5_f32": (c_int, [c_fp, c_int, c_fp, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
                                         c_fp, c_fp, c_ip, c_stream]),
+    "caspr_latent_dopri5_tape_f32": (c_int, [c_fp, c_int, c_fp, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
+                                             c_fp, c_fp, c_fp, c_ip, c_fp, c_fp, c_stream]),
+    "caspr_latent_dopri5_adjoint_f32": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_ip, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
+                                                c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_stream]),
     "caspr_latent_team_ws_bytes": (c_long, [c_int]),
     "caspr_latent_rk4_team_f32": (c_int, [c_fp, c_int, c_fp, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
                                           ctypes.c_void_p, c_long, c_stream]),

@@ -237,7 +237,7 @@ class CaSPR(nn.Module):
         if self.pretrain_tnocs:
             return
         # latent_method="dopri5": the latent ODE integrates to latent_rtol / latent_atol (the reference's 1e-3) with the adaptive kernel
-        # (inference only; per-sequence error control); the guard and calibrate_rk4_steps skip it, as they skip a dopri5 block
+        # (per-sequence error control; under autograd only with config.train_latent_dopri5); the guard and calibrate_rk4_steps skip it, as they skip a dopri5 block
         self.latent_ode = LatentODE(input_size=self.motion_feat_size, hidden_size=ode_hidden_size, num_layers=2,
                                     nonlinearity=nn.Tanh, rk4_steps=latent_rk4_steps, method=latent_method, rtol=latent_rtol, atol=latent_atol)
         self.cnf_args = PointCNFArgs()

@@ -4,13 +4,21 @@ Same parameter tree, including the reference's double registration of the dynami
 `ode_func.*` and `solver.ode_func.*` (latent_ode_model.py:36-38,81) and the `_num_evals` buffer.
 DEVIATION (documented): the reference integrates with adaptive dopri5 at rtol=atol=1e-3
 (latent_ode_model.py:38,83); this build runs `steps` RK4 steps per requested interval by default.  method="dopri5" integrates
-to rtol / atol with the adaptive kernel instead (ops.latent_dopri5: inference only, error control per sequence).
+to rtol / atol with the adaptive kernel instead (ops.latent_dopri5: error control per sequence).  Under autograd
+that option refuses unless config.train_latent_dopri5 is on; then forward / solve_at run the solve's autograd node
+(train/flow_grad.py: LatentSolveDopri5 -- the reference trains through odeint_adjoint on dopri5, latent_ode_model.py:9,85-99): the
+same launch and bits, and the gradient of its own accepted steps held fixed.
 """
 import torch
 import torch.nn as nn
 
 from .. import ops
+from ..config import config as _cfg
 from ..utils.weight_cache import WeightCache
+
+TRAIN_DOPRI5 = _cfg.train_latent_dopri5      # True: method="dopri5" under autograd runs LatentSolveDopri5 instead of refusing
+_NO_GRAD = ("LatentODE(method='dopri5') is an inference option: no gradient through the adaptive solve (training keeps RK4; "
+            "config.train_latent_dopri5 / models.latent_ode_model.TRAIN_DOPRI5 trains through it)")
 
 
 class LatentODE(nn.Module):
@@ -27,9 +35,10 @@ class LatentODE(nn.Module):
         self.augment_size = augment_size
         self.output_size = input_size + self.augment_size
         self.rk4_steps = rk4_steps
-        self.method = method          # "dopri5": forward / solve_at integrate to rtol / atol (inference only)
+        self.method = method          # "dopri5": forward / solve_at integrate to rtol / atol (under autograd only with TRAIN_DOPRI5)
         self.rtol, self.atol = rtol, atol
         self.max_attempts = max_attempts
+        self.train_max_steps = 64     # dopri5 under autograd: accepted steps per sequence the tape holds (a fuller sequence ends unfinished)
         self.last_nfe_per_sequence = None    # dopri5: (B,) int32 device tensor of the last solve
         self.ode_func = DynamicsNet(input_size=self.output_size, hidden_size=hidden_size, num_layers=num_layers, nonlinearity=nonlinearity)
         self.solver = ODESolver(self.ode_func, method='dopri5', rtol=1e-3, atol=1e-4)
@@ -57,9 +66,9 @@ class LatentODE(nn.Module):
         if z0.shape[1] != self.input_size:
             raise ValueError("expected %d latent dims, got %d" % (self.input_size, z0.shape[1]))
         if torch.is_grad_enabled() and (z0.requires_grad or any(p.requires_grad for p in self.ode_func.parameters())):
-            if self.method == "dopri5":
-                raise ValueError("LatentODE(method='dopri5') is an inference option: no gradient through the adaptive solve (training keeps RK4)")
-            from ..train.flow_grad import latent_solve_train                                    # differentiable RK4 (training)
+            if self.method == "dopri5" and not TRAIN_DOPRI5:
+                raise ValueError(_NO_GRAD)
+            from ..train.flow_grad import latent_solve_train                                    # differentiable RK4 / dopri5 (training)
             return latent_solve_train(self, z0, t)
         if self.method == "dopri5":
             return self.solve_dopri5(z0, t.detach().float().contiguous())
@@ -102,7 +111,10 @@ class LatentODE(nn.Module):
             plan = self.plan_times(time_tensor)
         if self.method == "dopri5":
             if torch.is_grad_enabled() and z0.requires_grad:
-                raise ValueError("LatentODE(method='dopri5') is an inference option: no gradient through the adaptive solve (training keeps RK4)")
+                if not TRAIN_DOPRI5:
+                    raise ValueError(_NO_GRAD)
+                from ..train.flow_grad import latent_solve_train
+                return latent_solve_train(self, z0, plan["sorted_t"])[plan["rows"], plan["pos"], :]
             return self.solve_dopri5(z0, plan["sorted_t"])[plan["rows"], plan["pos"], :]
         out = ops.latent_rk4(z0, plan["sorted_t"], self.rk4_steps, self._weights())            # (B, B*T, H)
         self.ode_func._num_evals.copy_(plan["evals"])                                           # evaluations actually run

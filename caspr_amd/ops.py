@@ -1098,12 +1098,38 @@ LATENT_DP5_TRACE_HEAD, LATENT_DP5_TRACE_ROW = 8, 4      # include/caspr_hip.h: t
 def _latent_dp5_report(records):
     for words, budget in records:
         if not all(words):
+            if isinstance(budget, tuple):        # the taping launch (train_ops.latent_dopri5_tape): (max_attempts, max_steps)
+                raise _lib.CasprHipError("caspr_latent_dopri5_tape_f32 (code %d, CASPR_ENOCONV): %d of %d sequences had not reached the last time stamp after "
+                                         "max_attempts = %d attempts or max_steps = %d accepted (taped) steps; the rows of the stamps they did not reach "
+                                         "hold NaN, and so will their dL/dz0 rows.  Raise LatentODE.train_max_steps (the tape's capacity), max_attempts "
+                                         "or the tolerance" % ((-4, words.count(0), len(words)) + budget))
             raise _lib.CasprHipError("caspr_latent_dopri5_f32 (code %d, CASPR_ENOCONV): %d of %d sequences had not reached the last time stamp after "
                                      "max_attempts = %d attempts; the rows of the stamps they did not reach hold NaN.  Raise max_attempts or the "
                                      "tolerance" % (-4, words.count(0), len(words), budget))
 
 
 _latent_dp5 = _Deferred(_latent_dp5_report)
+
+
+def _latent_dp5_args(who, z0, times, rtol, atol, wts, max_attempts):
+    """The argument checks of the adaptive latent solve, shared with its taping launch (train_ops.latent_dopri5_tape)
+    -> (B, D, H, rtol, atol, max_attempts)."""
+    _chk_f32(times, *[w for w in wts[1::2]])
+    if not z0.is_cuda or z0.dtype != torch.float32 or z0.dim() != 2 or z0.stride(1) != 1:
+        raise ValueError("%s: z0 must be a float32 GPU (B,D) tensor with unit column stride" % who)
+    _on_current_device(z0)
+    B = z0.shape[0]
+    D, H = wts[0].cin, wts[0].cout
+    if z0.shape[1] != D:
+        raise ValueError("%s: z0 has %d columns, the dynamics net expects %d" % (who, z0.shape[1], D))
+    if times.dim() != 1 or times.shape[0] < 1 or B < 1:
+        raise ValueError("%s: times must be a non-empty (Tu,) tensor and z0 hold at least one sequence" % who)
+    rtol, atol, max_attempts = float(rtol), float(atol), int(max_attempts)
+    if not (0 < rtol < float("inf") and 0 < atol < float("inf")):
+        raise ValueError("%s: rtol and atol must be positive and finite, got %r / %r" % (who, rtol, atol))
+    if max_attempts < 1:
+        raise ValueError("%s: max_attempts must be positive, got %d" % (who, max_attempts))
+    return B, D, H, rtol, atol, max_attempts
 
 
 def latent_dopri5(z0, times, rtol, atol, wts, max_attempts=1000, return_trace=False):
@@ -1115,23 +1141,10 @@ def latent_dopri5(z0, times, rtol, atol, wts, max_attempts=1000, return_trace=Fa
     Never synchronises and runs under stream capture.  A sequence that has not reached the last stamp after max_attempts attempts
     leaves NaN in the rows it did not reach; CasprHipError is raised by the next solve on the stream or by check_deferred_errors()
     (not tracked under capture, as latent_rk4)."""
-    _chk_f32(times, *[w for w in wts[1::2]])
-    if not z0.is_cuda or z0.dtype != torch.float32 or z0.dim() != 2 or z0.stride(1) != 1:
-        raise ValueError("latent_dopri5: z0 must be a float32 GPU (B,D) tensor with unit column stride")
-    _on_current_device(z0)
-    B = z0.shape[0]
-    D, H = wts[0].cin, wts[0].cout
-    if z0.shape[1] != D:
-        raise ValueError("latent_dopri5: z0 has %d columns, the dynamics net expects %d" % (z0.shape[1], D))
-    if times.dim() != 1 or times.shape[0] < 1 or B < 1:
-        raise ValueError("latent_dopri5: times must be a non-empty (Tu,) tensor and z0 hold at least one sequence")
-    rtol, atol, max_attempts = float(rtol), float(atol), int(max_attempts)
-    if not (0 < rtol < float("inf") and 0 < atol < float("inf")):
-        raise ValueError("latent_dopri5: rtol and atol must be positive and finite, got %r / %r" % (rtol, atol))
-    if max_attempts < 1:
-        raise ValueError("latent_dopri5: max_attempts must be positive, got %d" % max_attempts)
+    B, D, H, rtol, atol, max_attempts = _latent_dp5_args("latent_dopri5", z0, times, rtol, atol, wts, max_attempts)
     if torch.is_grad_enabled() and (z0.requires_grad or times.requires_grad):
-        raise ValueError("latent_dopri5: no gradient through the adaptive solve (training keeps RK4)")
+        raise ValueError("latent_dopri5: no gradient through the adaptive solve (training keeps RK4; config.train_latent_dopri5 trains through it "
+                         "on LatentODE(method='dopri5'))")
     Tu = times.shape[0]
     out = torch.empty(B, Tu, D, device=z0.device, dtype=torch.float32)
     trace = torch.empty(B, LATENT_DP5_TRACE_HEAD + LATENT_DP5_TRACE_ROW * max_attempts, device=z0.device, dtype=torch.float32) if return_trace else None

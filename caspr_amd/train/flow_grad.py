@@ -631,6 +631,59 @@ class LatentSolve(torch.autograd.Function):
         return (gz, None, None) + tuple(grads)
 
 
+class LatentSolveDopri5(torch.autograd.Function):
+    """The ADAPTIVE latent solve (LatentODE(method="dopri5"); latent_ode_model.py:45-70,85-99, where the reference trains through
+    odeint_adjoint on dopri5) as one autograd node: forward = train_ops.latent_dopri5_tape, the launch and the bits of
+    ops.latent_dopri5 plus (z_n, dt_n) of every accepted step; backward = train_ops.latent_dopri5_adjoint, one launch, then one
+    weight-gradient product per layer over all evaluations' rows, as LatentSolve._backward_team.
+    The gradient is the one of the forward's own discrete map with its accepted step sequence held fixed: every dt, stage time,
+    interpolation abscissa and accept / reject decision is a constant, rejected attempts and the initial-step selection contribute
+    nothing.  Left out: the dependence of the step sizes on z0 and the parameters (the sensitivity of the discretisation error, of the
+    order of the tolerance) -- the reference's continuous adjoint never differentiates its controller either.
+    z0 (B,D), tt (Tu,) ascending device times, rtol, atol, max_attempts, max_steps, then w0, b0, ..., w3, b3 -> (B,Tu,D).
+    One stamp, or all stamps equal: the launch makes no attempt (two evaluations, the initial-step selection's, as in inference); the
+    output is z0 at every stamp, dL/dz0 the sum of gout over the stamps (in f64, rounded once), the parameter gradients exactly zero.
+    The stamps' values are never read on the host; with one stamp the backward skips its launch.
+    Backward memory: B (1 + 6 max_steps) rows x (3 H + 2 roundup4(D)) floats x 2, freed after the products: about 39 MB at B = 8 and
+    315 MB at B = 64 for max_steps = 64, H = 512.  The accepted count is not read on the host to shrink it.
+    `info` of the last forward (trace views and counters, device tensors) is left in LatentSolveDopri5.last_info."""
+
+    last_info = None
+
+    @staticmethod
+    def forward(ctx, z0, tt, rtol, atol, max_attempts, max_steps, *wb):
+        ws, bs = wb[0::2], wb[1::2]
+        if any(b is None for b in bs):
+            raise ValueError("LatentSolveDopri5: the dynamics net's four layers carry biases (latent_ode_model.py:139-147)")
+        ctx.ws = ws
+        ctx.single = tt.shape[0] == 1
+        pk = [_packed(w, False) for w in ws]
+        bd = [b.detach().contiguous() for b in bs]
+        wts = [x for w, b in zip(pk, bd) for x in (w, b)]
+        out, info, tape = T.latent_dopri5_tape(z0.detach(), tt, rtol, atol, wts, max_attempts=max_attempts, max_steps=max_steps)
+        LatentSolveDopri5.last_info = info
+        ctx.tape, ctx.wts = tape, wts
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        ws = ctx.ws
+        if ctx.single:
+            zeros = [g for w in ws for g in (torch.zeros_like(w), torch.zeros(w.shape[0], device=w.device, dtype=w.dtype))]
+            return (gout[:, 0].contiguous(), None, None, None, None, None) + tuple(zeros)
+        pkt = [_packed(w, True) for w in (ws[3], ws[2], ws[1], ws[0])]
+        gz, inputs, deltas = T.latent_dopri5_adjoint(gout.contiguous(), ctx.tape, ctx.wts, pkt)
+        grads = []
+        for i in range(4):
+            cout, cin = ws[i].shape
+            dw = torch.empty(cout, cin, device=gz.device, dtype=torch.float32)
+            db = torch.empty(cout, device=gz.device, dtype=torch.float32)
+            T.conv1x1_wgrad(deltas[i].view(1, deltas[i].shape[0], -1), inputs[i].view(1, inputs[i].shape[0], -1), cin, cout, dw, db)
+            grads += [dw, db]
+        ctx.tape = ctx.wts = None
+        return (gz, None, None, None, None, None) + tuple(grads)
+
+
 def latent_solve_layers(lat, z0, times):
     """The same solve with one autograd node per layer call (`linear_rows`) and torch.autograd's own reverse sweep: what
     LatentSolve is checked against (tests/test_hip_train.py)."""
@@ -666,13 +719,20 @@ BLOCK_NODE_REG = _cfg.train_cnf_block_node_reg   # True (with BLOCK_NODE): cnf_b
 
 
 def latent_solve_train(lat, z0, times):
-    """z0 (B,D) differentiable, times (Tu,) ascending -> (B,Tu,D); first output is z0 itself."""
+    """z0 (B,D) differentiable, times (Tu,) ascending -> (B,Tu,D); first output is z0 itself.  lat.method "dopri5" (with
+    config.train_latent_dopri5, which LatentODE checks): the adaptive solve's node, LatentSolveDopri5."""
     tt = times.detach().float()
+    wb = []
+    for i in (0, 2, 4, 6):
+        l = lat.ode_func.dynamics_net[i]
+        wb += [l.weight, l.bias]
+    if lat.method == "dopri5":
+        out = LatentSolveDopri5.apply(z0, tt.contiguous(), lat.rtol, lat.atol, lat.max_attempts, lat.train_max_steps, *wb)
+        info = LatentSolveDopri5.last_info
+        lat.last_nfe_per_sequence = info["nfe"]           # measured, as LatentODE.solve_dopri5: element-wise device ops, no host read
+        lat.ode_func._num_evals.mul_(0).add_(info["nfe"].max().to(lat.ode_func._num_evals.dtype))
+        return out
     if LATENT_NODE:
-        wb = []
-        for i in (0, 2, 4, 6):
-            l = lat.ode_func.dynamics_net[i]
-            wb += [l.weight, l.bias]
         out = LatentSolve.apply(z0, tt, lat.rk4_steps, *wb)
     else:
         out = latent_solve_layers(lat, z0, times)

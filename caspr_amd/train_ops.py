@@ -166,6 +166,73 @@ def gn_rows_bwd(y, ns, C, gamma, beta, relu, mean, rstd, dgamma, dbeta, da=None,
     return out
 
 
+def latent_dopri5_tape(z0, times, rtol, atol, wts, max_attempts=1000, max_steps=64):
+    """ops.latent_dopri5 with the step tape its reverse sweep needs (caspr_latent_dopri5_tape_f32, csrc/ode_latent_dp5.hip: the same
+    kernel text; latent_ode_model.py:45-70): same arguments, and out, trace and counters are that call's bits.
+    -> out (B,Tu,D), info (the dict of ops.latent_dopri5(return_trace=True)), tape = {"counters" (B,4) int32, "z" (B,max_steps,D) the start
+    state of every accepted step, "dt" (B,max_steps) its size, "times", "max_steps"}.  Never synchronises.  A sequence that would accept
+    more than max_steps steps stops like one that used up max_attempts (finished = 0, NaN in the rows it did not reach); the deferred
+    CasprHipError names both budgets."""
+    B, D, H, rtol, atol, max_attempts = ops._latent_dp5_args("latent_dopri5_tape", z0, times, rtol, atol, wts, max_attempts)
+    max_steps = int(max_steps)
+    if max_steps < 1:
+        raise ValueError("latent_dopri5_tape: max_steps must be positive, got %d" % max_steps)
+    Tu, dev = times.shape[0], z0.device
+    HEAD, ROW = ops.LATENT_DP5_TRACE_HEAD, ops.LATENT_DP5_TRACE_ROW
+    out = torch.empty(B, Tu, D, device=dev, dtype=torch.float32)
+    trace = torch.empty(B, HEAD + ROW * max_attempts, device=dev, dtype=torch.float32)
+    counters = torch.empty(B, 4, device=dev, dtype=torch.int32)
+    tz = torch.zeros(B, max_steps, D, device=dev, dtype=torch.float32)
+    tdt = torch.zeros(B, max_steps, device=dev, dtype=torch.float32)
+    ptrs = [_p(w.data) if isinstance(w, ops.PackedWeight) else _p(w) for w in wts]
+    with ops._latent_dp5.on(dev) as status:
+        with ops.timed("latent_dopri5_tape"):
+            _lib.check(_lib.load().caspr_latent_dopri5_tape_f32(_p(z0), z0.stride(0), _p(times), B, Tu, D, H, rtol, atol, max_attempts, max_steps, *ptrs,
+                                                                _p(out), _p(trace), _p(counters), _p(tz), _p(tdt), _stream()), "caspr_latent_dopri5_tape_f32")
+        status.post(counters[:, 3], (max_attempts, max_steps))
+    info = {"d0": trace[:, 0], "d1": trace[:, 1], "d2": trace[:, 2], "h0": trace[:, 3], "dt0": trace[:, 4],
+            "attempts": trace[:, HEAD:].view(B, max_attempts, ROW), "accepted": counters[:, 0], "rejected": counters[:, 1], "nfe": counters[:, 2]}
+    return out, info, {"counters": counters, "z": tz, "dt": tdt, "times": times, "max_steps": max_steps}
+
+
+def latent_dopri5_adjoint(gout, tape, wts, wts_t):
+    """The reverse sweep of latent_dopri5_tape in one launch (caspr_latent_dopri5_adjoint_f32, csrc/ode_latent_dp5_adjoint.inc): the
+    gradient of the solve's own discrete map, accepted steps held fixed.  gout (B,Tu,D) = dL/d(out); tape: that call's; wts: the solve's
+    [PackedWeight0, b0, .., PackedWeight3, b3]; wts_t: PackedWeights of the TRANSPOSED W3, W2, W1, W0 (in that order).
+    -> gz (B,D) = dL/dz0 (NaN rows for unfinished sequences), inputs = [x (R,xw), h1, h2, h3 (R,H)], deltas = [d0, d1, d2 (R,H), d3 (R,xw)]:
+    R = B (1 + 6 max_steps) rows, zero where a sequence made no evaluation; dW_l = deltas[l]^T inputs[l], db_l = colsum(deltas[l]).
+    Memory: R x (3 H + 2 roundup4(D)) floats x 2 (inputs and deltas): about 39 MB at B = 8 and 315 MB at B = 64 with max_steps = 64,
+    H = 512.  Never synchronises and reads no count on the host."""
+    _chk_f32(gout, *[w for w in wts[1::2]])
+    counters, tz, tdt, times, max_steps = tape["counters"], tape["z"], tape["dt"], tape["times"], tape["max_steps"]
+    _chk_f32(tz, tdt, times)
+    _chk_i32(counters)
+    B, Tu, D = gout.shape
+    H = wts[0].cout
+    if wts[0].cin != D or tuple(tz.shape) != (B, max_steps, D) or tuple(tdt.shape) != (B, max_steps) or tuple(counters.shape) != (B, 4) or times.shape[0] != Tu:
+        raise ValueError("latent_dopri5_adjoint: gout (B,Tu,D) = %s does not match the tape (z %s, dt %s, counters %s, %d stamps) or the dynamics net (%d inputs)"
+                         % (tuple(gout.shape), tuple(tz.shape), tuple(tdt.shape), tuple(counters.shape), times.shape[0], wts[0].cin))
+    shapes = [(w.cout, w.cin) for w in wts_t]
+    if shapes != [(H, D), (H, H), (H, H), (D, H)]:
+        raise ValueError("latent_dopri5_adjoint: wts_t must pack W3^T (H,D), W2^T, W1^T (H,H), W0^T (D,H), got %s" % (shapes,))
+    if not gout.is_contiguous():
+        raise ValueError("latent_dopri5_adjoint: gout must be contiguous")
+    dev = gout.device
+    R, xw = B * (1 + 6 * max_steps), (D + 3) // 4 * 4
+    inputs = [torch.zeros(R, xw, device=dev, dtype=torch.float32)] + [torch.zeros(R, H, device=dev, dtype=torch.float32) for _ in range(3)]
+    deltas = [torch.zeros(R, H, device=dev, dtype=torch.float32) for _ in range(3)] + [torch.zeros(R, xw, device=dev, dtype=torch.float32)]
+    gz = torch.empty(B, D, device=dev, dtype=torch.float32)
+    ptrs = [_p(w.data) if isinstance(w, ops.PackedWeight) else _p(w) for w in wts]
+    # the launch reports nothing of its own: an unfinished sequence was posted by the taping launch (the _latent_dp5 channel) and is raised
+    # by the next solve on the stream or by ops.check_deferred_errors(), not from inside a backward pass
+    with ops.timed("latent_dopri5_adjoint"):
+        _lib.check(_lib.load().caspr_latent_dopri5_adjoint_f32(_p(gout), _p(times), B, Tu, D, H, max_steps, _p(counters), _p(tz), _p(tdt), *ptrs,
+                                                               *[_p(w.data) for w in wts_t], _p(inputs[0]), xw, _p(inputs[1]), _p(inputs[2]),
+                                                               _p(inputs[3]), _p(deltas[0]), _p(deltas[1]), _p(deltas[2]), _p(deltas[3]), _p(gz),
+                                                               _stream()), "caspr_latent_dopri5_adjoint_f32")
+    return gz, inputs, deltas
+
+
 def cnf_train_fwd(y, logp, e, hyper, tcol, w0, b0, w1x, b1, w2x, b2, w3, b3, t_end, steps):
     """Training forward of one CNF block in one launch (caspr_cnf_train_fwd_f32): y, e (BT,n,3), logp (BT,n,1), hyper (BT, >= 3078) and
     tcol as ops.cnf_rk4 takes them, w1x / w2x = ops.pack_cnf_x6, t_end a one-element DEVICE tensor.

@@ -162,6 +162,34 @@ int caspr_latent_rk4_team_adjoint_f32(const float *gout, const float *times, int
                                       float *d1, float *d2, float *d3, int xw, float *gz, void *ws, long ws_bytes,
                                       void *stream);
 
+/* The latent ODE's training path through its ADAPTIVE solve (latent_ode_model.py:45-70,85-99: odeint_adjoint on dopri5 in the reference;
+ * here the gradient of the solve's own discrete map with the accepted step sequence held fixed).
+ * caspr_latent_dopri5_tape_f32: caspr_latent_dopri5_f32 (include/caspr_hip.h: same arguments, same out / trace / counters, bit for bit)
+ *   that also leaves, per sequence and accepted step n, the step's start state in tape_z (B, max_steps, D) and its size in tape_dt
+ *   (B, max_steps); the accepted count is counters[4 b].  A sequence whose next accepted step would not fit max_steps stops like one
+ *   that used up max_attempts: finished = 0, NaN in the rows it did not reach.
+ * caspr_latent_dopri5_adjoint_f32: the reverse sweep, one launch.  gout (B, Tu, D) = dL/d(out) -> gz (B, D) = dL/dz0 and, per layer, the
+ *   input rows x (R, xw), h1 / h2 / h3 (R, H) and delta rows d0 / d1 / d2 (R, H), d3 (R, xw) of all evaluations, R = B (1 + 6 max_steps),
+ *   xw >= D a multiple of 4: evaluation e of sequence b (6 n + s - 1 for stage s of step n, 6 N for the final state) is row
+ *   b (1 + 6 max_steps) + e.  Rows a sequence does not use are NOT written: zero-fill all eight buffers.  dW_l = d_l^T input_l and
+ *   db_l = colsum(d_l) follow as ONE caspr_conv1x1_wgrad_f32 per layer over the R rows.  w0p .. b3 as the solve takes them, w3tp .. w0tp:
+ *   caspr_pack_weight of the TRANSPOSED weights (W3^T (H, D) .. W0^T (D, H)); counters, tape_z, tape_dt, times, max_steps: the taping
+ *   launch's.  An unfinished sequence (finished = 0) writes no rows and gets NaN in its gz row.
+ * Both: D <= 64, H <= 512, H % 64 == 0, any B (CASPR_EUNSUP otherwise); no workspace, no inter-workgroup traffic; deterministic, and a
+ * sequence's results do not depend on the batch around it.                                                                         */
+int caspr_latent_dopri5_tape_f32(const float *z0, int ldz, const float *times, int B, int Tu, int D, int H, float rtol,
+                                 float atol, int max_attempts, int max_steps, const float *w0p, const float *b0,
+                                 const float *w1p, const float *b1, const float *w2p, const float *b2, const float *w3p,
+                                 const float *b3, float *out, float *trace, int32_t *counters, float *tape_z,
+                                 float *tape_dt, void *stream);
+int caspr_latent_dopri5_adjoint_f32(const float *gout, const float *times, int B, int Tu, int D, int H, int max_steps,
+                                    const int32_t *counters, const float *tape_z, const float *tape_dt, const float *w0p,
+                                    const float *b0, const float *w1p, const float *b1, const float *w2p, const float *b2,
+                                    const float *w3p, const float *b3, const float *w3tp, const float *w2tp,
+                                    const float *w1tp, const float *w0tp, float *rows_x, int xw, float *rows_h1,
+                                    float *rows_h2, float *rows_h3, float *d0, float *d1, float *d2, float *d3, float *gz,
+                                    void *stream);
+
 /* Gated softplus layer of the CNF's ODE function (ConcatSquashLinear + Softplus, diffeq_layers.py:83-90,
  * odefunc.py:98-105) on value and tangent rows of Z (2R, ldz) = the layer's matrix product; frame f = p / n has its
  * own gate / beta rows (hyper networks of the context).  Row layout: blk = R puts the value of point p in row p and its
